@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Sub-GC hot path on MI355X: train fwd+bwd images/s (Sub_GC_Kar, BASELINE.json configs[1]).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -9,6 +9,18 @@ One rank per GPU.  A step = one pass of the hot path over one synthetic batch th
 resident in HBM: LossWrapper forward (fusion -> GCN -> sGPN -> attention-LSTM decoder -> NLL),
 backward, and for N > 1 the RCCL all-reduce of the flat gradient bucket.  Per-GPU batch is fixed
 (weak scaling); `value` = images of all ranks / max-over-ranks wall time.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step,
+final_loss, config).  `--full` adds everything else to that line: the roofline, the HBM-bound kernel
+families, fwd+bwd without the update, host enqueue time, the unpacked decoder, the other GEMM modes,
+the decode legs, the CPU baselines and the other BASELINE configs (N = 1), the communication report
+and the sharded decode (N > 1).  `--dump-outputs DIR` writes what the last timed step left to its
+caller as DIR/<name>.npy (fp32): the losses and a fixed, seeded sample of the optimizer's moments
+(of the gradients with --no-optimizer).  Inputs, weights and dropout keys are seeded, and every step
+starts from the same weights (the optimizer sweep runs in full with learning rate 0): the backward's
+scatter reductions (embedding, pooling, sub-graph score) add with float atomics, so gradients match
+only to rounding, and applied updates would carry those last bits into a trajectory that drifts apart
+from run to run.  So two runs, or two builds, with the same arguments compute the same outputs.
 
 `roofline`: the dominant kernel is the fp32 MFMA GEMM (gemm_f32_kernel): every launch inside the
 timed region is bracketed by HIP events on its own stream (C-ABI profiling hook), so
@@ -71,6 +83,29 @@ CONFIGS = {
 def lw_args(b):
     return (b["fc_feats"], b["att_feats"], b["labels"], b["masks"], b["att_masks"], None, None, None, b["obj_dist"], None,
             b["rel_ind"], None, b["pred_dist"], b["gpn_obj_ind"], b["gpn_pred_ind"], b["gpn_nrel_ind"], b["gpn_pool_mtx"])
+
+
+DUMP_SAMPLE = 1 << 22           # --dump-outputs: elements kept of a flat buffer larger than this (16 MB of fp32 each)
+
+
+def dump_outputs(path, out, loss, model, adam):
+    """What one timed step hands its caller, as fp32 .npy files: the LossWrapper losses, the summed loss, and the optimizer's first and
+    second moments after the sweep (`adam_m`, `adam_v`: the sweep zeroes the gradient buffer; with --no-optimizer nothing consumes
+    the gradients, so the flat gradient buffer, `grads`).  A buffer of more than DUMP_SAMPLE elements is written at a fixed set of
+    sorted indices (seed 0), the same for every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: v for k, v in out.items() if v is not None}
+    arrays["loss"] = loss
+    flats = {"adam_m": adam.m, "adam_v": adam.v} if adam is not None else {"grads": model.flat_grads}
+    n = next(iter(flats.values())).numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).unique().to(loss.device)
+    for k, v in flats.items():
+        arrays[k] = v if idx is None else v[idx]
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v.detach().float().cpu().numpy())
 
 
 def effective_cores():
@@ -497,6 +532,9 @@ def main():
     ap.add_argument("--dedup", type=int, default=-1, help="experiment (Full-GC): opt.dedup_att_embed (1 = att_embed once per node row + masked gather per copy, 0 = on the replicated rows)")
     ap.add_argument("--no-p8", action="store_true", help="experiment (bf16 configs): SUBGC_GEMM_NO_P8 on every subgc_gemm_bf16 call -- the ring forms only (A/B of the eight-phase form)")
     ap.add_argument("--ss-prob", type=float, default=0.0, help="scheduled-sampling probability (train.py raises it from epoch 5; the headline workload is 0)")
+    ap.add_argument("--full", action="store_true", help="also the roofline, per-family and CPU-baseline legs, the other modes and configs "
+                    "(N = 1), the communication report and sharded decode (N > 1); a plain run reports the headline figure only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (fp32, <= 64 MB in all)")
     a = ap.parse_args()
     cfg = CONFIGS[a.config]
     a.batch = a.batch or cfg["batch"]
@@ -533,9 +571,12 @@ def main():
         model.ss_prob = a.ss_prob
     lw = models.LossWrapper(model, None)
     batch = {k: v.to(dev) for k, v in synthetic.make_train_batch(a.batch, seed=1000 + rank, **cfg["data"]).items()}
-    adam = None if a.no_optimizer else parallel.FlatAdam(model)      # a training step ends with the parameter update (misc/utils.py:174-200 + Adam)
+    # a training step ends with the parameter update (misc/utils.py:174-200 + Adam): the whole clip + Adam sweep, at learning rate 0 so
+    # that every step starts from the seeded weights (module docstring: the steps' inputs and outputs are the same in every run)
+    adam = None if a.no_optimizer else parallel.FlatAdam(model, lr=0.0)
     red = parallel.GradBucketReducer(model, optimizer=adam)          # the clip norm is accumulated slice by slice as the slices become final
     one = ops.fill_(torch.empty((), device=dev, dtype=torch.float32), 1.0)
+    last = {}                                             # the LossWrapper outputs of the latest step (--dump-outputs)
 
     def step():
         red.prepare()
@@ -545,6 +586,7 @@ def main():
         red.finish(average=adam is None)                 # with the optimizer on, 1/world rides in its sweep
         if adam is not None:
             adam.step(grad_scale=1.0 / world, zero_grad=True)        # step + the iteration's optimizer.zero_grad() in one sweep
+        last["out"] = out
         return loss
 
     def timed_sampled(n_steps):
@@ -571,22 +613,44 @@ def main():
     fence()
     # Roofline events: every GEMM launch of the SAMPLED steps of the timed region is bracketed by HIP events on its launch
     # stream.  Bracketing all K steps costs 4-5 % of the step (each event pair drains the launch pipeline between kernels), so
-    # two of the K timed steps carry the events (330 launches) and the others run as the product does.
-    sampled = sorted({0, a.steps // 2}) if rank == 0 else []
+    # two of the K timed steps carry the events (330 launches) and the others run as the product does.  --full only.
+    sampled = sorted({0, a.steps // 2}) if rank == 0 and a.full else []
     t0 = time.perf_counter()
     for i in range(a.steps):
-        if rank == 0:
+        if sampled:
             _lib.prof_enable("gemm", i in sampled)
         loss = step()
     fence()
     elapsed = time.perf_counter() - t0
-    if rank == 0:
+    if sampled:
         _lib.prof_enable("gemm", False)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss.item())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, last["out"], loss, model, adam)
+    ms_per_step = 1e3 * elapsed / a.steps
+    imgs = world * a.batch
+    res = {
+        "metric": cfg["metric"], "value": round(imgs * a.steps / elapsed, 2), "unit": "images/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": cfg["dtype"], "data": "synthetic",
+        "config": {"workload": cfg["workload"],
+                   "images_per_gpu": a.batch, "global_images": imgs, "parallelism": f"dp{world}" if world > 1 else "single",
+                   "decoder": "packed (length-sorted, loss-only: masked-out steps skipped; identical loss and gradients)",
+                   "includes": "fwd + bwd" + (" + RCCL grad all-reduce" if world > 1 else "") + (" + fused clip+Adam" if adam else "")
+                               + (f" + scheduled sampling p={a.ss_prob} (per-step logits and draws)" if a.ss_prob > 0 else "")},
+        "final_loss": round(final_loss, 4),
+    }
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # one untimed accounting step: exact (ragged-aware) GEMM FLOPs.  EVERY rank runs it -- the step contains the gradient
     # all-reduce, so a rank-0-only step would wait for its peers forever
@@ -600,20 +664,7 @@ def main():
         alg_bytes_launch = ops.FLOPS["gemm_bytes"] / max(ops.FLOPS["gemm_calls"], 1)
         n_s = max(len(sampled), 1)
         traffic, traffic_note = pmc_traffic(a.config, a.batch, world, n_launch // n_s)
-        ms_per_step = 1e3 * elapsed / a.steps
-        imgs = world * a.batch
-        res = {
-            "metric": cfg["metric"], "value": round(imgs * a.steps / elapsed, 2), "unit": "images/s",
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(ms_per_step, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": cfg["dtype"], "data": "synthetic",
-            "config": {"workload": cfg["workload"],
-                       "images_per_gpu": a.batch, "global_images": imgs, "parallelism": f"dp{world}" if world > 1 else "single",
-                       "decoder": "packed (length-sorted, loss-only: masked-out steps skipped; identical loss and gradients)",
-                       "includes": "fwd + bwd" + (" + RCCL grad all-reduce" if world > 1 else "") + (" + fused clip+Adam" if adam else "")
-                                   + (f" + scheduled sampling p={a.ss_prob} (per-step logits and draws)" if a.ss_prob > 0 else "")},
-            "roofline": roofline_block(cfg, a.batch, flops_step, alg_bytes_launch, n_launch, n_s, gemm_ms, ms_per_step, traffic, traffic_note, a.steps),
-            "final_loss": round(final_loss, 4),
-        }
+        res["roofline"] = roofline_block(cfg, a.batch, flops_step, alg_bytes_launch, n_launch, n_s, gemm_ms, ms_per_step, traffic, traffic_note, a.steps)
         pmc_path = os.path.join(ROOT, "profiles", "r02_pmc_gemm_f32.json")
         if headline and os.path.exists(pmc_path):                 # committed PMC passes over single shapes of the same kernel
             with open(pmc_path) as f:

@@ -5,6 +5,6 @@
 # the 15-part cut were judged in round 6.  Restore the library afterwards (python sub-gc_amd/build.py --force).
 R=${GRAFT_REPO_ROOT:-.}; L=$R/sub-gc_amd/subgc
 for r in $(seq 1 ${2:-2}); do for v in a b; do cp $L/lib_$v.so $L/libsubgc_hip.so; for C in ${1:-full_gc_kar flickr kar}; do
-  python $R/bench.py --config $C --steps 10 --warmup 3 --no-cpu-baseline --no-decode --packed-only --no-other-configs 2>&1 | tail -1 | \
+  python $R/bench.py --full --config $C --steps 10 --warmup 3 --no-cpu-baseline --no-decode --packed-only --no-other-configs 2>&1 | tail -1 | \
     python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$v $C', d['value'], d['ms_per_step'], d['roofline']['gemm_ms_per_step'])"
 done; done; done

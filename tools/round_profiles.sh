@@ -5,10 +5,10 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 ROUND=${ROUND:-r06}
-python $R/bench.py > $O/${ROUND}_bench_n1.log 2>&1; tail -1 $O/${ROUND}_bench_n1.log > $R/profiles/${ROUND}_bench_n1.json
+python $R/bench.py --full > $O/${ROUND}_bench_n1.log 2>&1; tail -1 $O/${ROUND}_bench_n1.log > $R/profiles/${ROUND}_bench_n1.json
 cp $R/profiles/${ROUND}_bench_n1.json $O/${ROUND}_bench_n1.json          # profiles/ on the box is not merged back, gpurun_out/ is
 for C in full_gc_kar flickr kar_ss25; do
-  python $R/bench.py --config $C --steps 10 --warmup 3 > $O/${ROUND}_bench_$C.log 2>&1; tail -1 $O/${ROUND}_bench_$C.log > $O/${ROUND}_bench_$C.json
+  python $R/bench.py --full --config $C --steps 10 --warmup 3 > $O/${ROUND}_bench_$C.log 2>&1; tail -1 $O/${ROUND}_bench_$C.log > $O/${ROUND}_bench_$C.json
 done
 prof() {  # name, command...
   local name=$1; shift
@@ -16,13 +16,13 @@ prof() {  # name, command...
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$name -- "$@" > $O/prof_$name.log 2>&1
   timeout 120 python $R/tools/rocprof_summary.py $O/prof_$name $O/${ROUND}_${name}_kernel_stats.txt > /dev/null
 }
-prof train python $R/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-decode --packed-only --no-other-configs
-prof full_gc_kar python $R/bench.py --config full_gc_kar --steps 8 --warmup 2
-prof flickr python $R/bench.py --config flickr --steps 8 --warmup 2
+prof train python $R/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-decode --packed-only --no-other-configs
+prof full_gc_kar python $R/bench.py --full --config full_gc_kar --steps 8 --warmup 2
+prof flickr python $R/bench.py --full --config flickr --steps 8 --warmup 2
 prof decode python $R/tools/decode_bench.py
 for C in FETCH_SIZE WRITE_SIZE; do
   rm -rf $O/pmc_$C
-  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$C -- python $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-decode --packed-only --no-other-configs > $O/pmc_$C.log 2>&1
+  rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$C -- python $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-decode --packed-only --no-other-configs > $O/pmc_$C.log 2>&1
 done
 LPS=$(python -c "import json;print(json.load(open('$R/profiles/${ROUND}_bench_n1.json'))['roofline']['launches_per_step'])")
 ALG=$(python -c "import json;print(json.load(open('$R/profiles/${ROUND}_bench_n1.json'))['roofline']['algorithmic_bytes_per_launch'])")
@@ -32,7 +32,7 @@ python $R/tools/pmc_traffic.py $(find $O/pmc_FETCH_SIZE -name "*counter_collecti
 for C in full_gc_kar flickr kar_ss25; do
   for P in FETCH_SIZE WRITE_SIZE; do
     rm -rf $O/pmc_${C}_$P
-    rocprofv3 --pmc $P --kernel-trace --output-format csv -d $O/pmc_${C}_$P -- python $R/bench.py --config $C --steps 3 --warmup 2 --no-cpu-baseline --no-decode --packed-only > $O/pmc_${C}_$P.log 2>&1
+    rocprofv3 --pmc $P --kernel-trace --output-format csv -d $O/pmc_${C}_$P -- python $R/bench.py --full --config $C --steps 3 --warmup 2 --no-cpu-baseline --no-decode --packed-only > $O/pmc_${C}_$P.log 2>&1
   done
   LPS=$(python -c "import json;print(json.load(open('$O/${ROUND}_bench_$C.json'))['roofline']['launches_per_step'])")
   ALG=$(python -c "import json;print(json.load(open('$O/${ROUND}_bench_$C.json'))['roofline']['algorithmic_bytes_per_launch'])")
