@@ -13,8 +13,9 @@
  *   - all pointers are BORROWED device pointers owned by the caller (e.g. tensor.data_ptr());
  *     outputs / scratch are caller-allocated; row-major, fp32 unless noted, indices int64 where
  *     the reference uses LongTensor inputs and int32 for internal index structures;
- *   - re-entrant per stream: there is NO process-global scratch, mode or tuning state (no environment variable is read; the ONE
- *     exception is the opt-in profiling hook subgc_prof_enable / subgc_prof_collect below, a process-wide event log for bench.py) -- the entry points that can use a split-K scratch
+ *   - re-entrant per stream: there is NO process-global scratch or tuning state and no environment variable is read.  Three
+ *     process-wide switches exist, all off by default: the opt-in profiling hook subgc_prof_enable / subgc_prof_collect below (an
+ *     event log for bench.py), subgc_debug_bounds (index validation) and subgc_deterministic (fixed-order reductions) -- the entry points that can use a split-K scratch
  *     take `workspace, ws_bytes` as CALL arguments (subgc_gemm_workspace_bytes / subgc_gemm_bf16_workspace_bytes say how much
  *     a shape can use; NULL / smaller is legal), so calls on different streams only need different workspaces;
  *     subgc_last_error() returns a thread-local message for the last failing call on the calling thread;
@@ -49,6 +50,25 @@ const char* subgc_arch(void);
  * reference fails with an IndexError / AssertionError on a bad loader tensor.  Costs one launch and one stream synchronisation per
  * checked tensor; skipped on a capturing stream.  With the mode off the kernels keep their documented clamping behaviour.           */
 int subgc_debug_bounds(int on);
+/* Deterministic mode (off by default; returns the previous setting).  Process-wide, not thread-local (the autograd backward runs on
+ * its own thread), and read when a call ENQUEUES its kernels: a graph captured with the mode on keeps the deterministic forms.  While on,
+ * two calls with the same input values, shapes, pointer alignments and ws_bytes return bit-identical outputs, on any stream, under any
+ * load: every reduction of the training step sums in an order fixed by the shape alone (no float atomics).
+ *   - the scatter-adds (embedding gradient, row scatter-add, sub-graph pooling backward) build an inverted index in the workspace
+ *     (destination -> its source items in ascending order) and add each destination's fixed-order sum to it once;
+ *   - the clip-norm sum of squares, the score-head weight gradient, the column sums (colsum_*) and the two-pass BatchNorm (bn_fwd /
+ *     bn_bwd) write slab / workgroup partials and add them in a fixed order -- the slab plan no longer depends on pointer alignment,
+ *     on the slab count or on how much workspace was passed;
+ *   - entry points that add with float atomics and take no workspace (subgc_embed_bwd, subgc_scatter_add_rows, subgc_sumsq_f32,
+ *     subgc_subgraph_pool_bwd, subgc_gpn_score_bwd) return SUBGC_EINVAL naming their `_ws` sibling; a `_ws` sibling or colsum /
+ *     bn call whose workspace is too small returns SUBGC_EINVAL with the bytes it needs in subgc_last_error().  With the mode off
+ *     the `_ws` siblings launch exactly what their originals launch.
+ * The inverted index of the scatter-adds holds at most 262144 items per call (n, M or G * N): more is SUBGC_EINVAL in the mode.
+ * A weight-gradient GEMM with a bias gradient (subgc_gemm_f32 / subgc_gemm_bf16 families) whose bias sum falls back to subgc_colsum_*
+ * needs the colsum workspace in the mode (slabs x N floats): a NULL or short workspace is SUBGC_EINVAL there, legal with the mode off.
+ * GEMM dispatch is deterministic for a given shape, alignment and ws_bytes in either mode.  Out of the guarantee: the order of a
+ * cross-rank (RCCL) sum when the world size is above 1 -- the contract is per rank.                                                    */
+int subgc_deterministic(int on);
 
 /* ---- profiling hook used by bench.py (HIP events on the launch stream) -------------------
  * While enabled, every launch of kernel family `family` (see SUBGC_FAM_*) is bracketed by a
@@ -268,6 +288,11 @@ int subgc_subgraph_pool_fwd(const float* X, const int64_t* idx, int64_t idx_stri
 int subgc_subgraph_pool_bwd(const float* dout, const int64_t* idx, int64_t idx_stride, const float* w,
                             int64_t w_gstride, int64_t w_istride, const float* denom, const int32_t* img,
                             const int32_t* argmax, float* dX, int G, int N, int L, void* stream);
+/* subgc_subgraph_pool_bwd + the caller's scratch; x_rows = rows of dX.  Deterministic mode: inverted index over the (sub-graph, slot) pairs
+ * with a non-zero weight, each node row summed in ascending (g, i) order -- the layout of subgc_embed_bwd_ws with V = x_rows, n = G N, E = L */
+int subgc_subgraph_pool_bwd_ws(const float* dout, const int64_t* idx, int64_t idx_stride, const float* w, int64_t w_gstride,
+                               int64_t w_istride, const float* denom, const int32_t* img, const int32_t* argmax, float* dX,
+                               int G, int N, int L, int x_rows, void* workspace, size_t ws_bytes, void* stream);
 
 /* score head tail (gpn.py:54-57): z = <hid[g,:] * keep[g,:] * keep_scale, w2> + b2,
  * score = sigmoid(z), loss = mean BCE(score, target) with target[g] = g < G/2 (log clamped at
@@ -277,6 +302,11 @@ int subgc_gpn_score_fwd(const float* hid, const uint8_t* keep, float keep_scale,
 int subgc_gpn_score_bwd(const float* hid, const uint8_t* keep, float keep_scale, const float* w2,
                         const float* score, const float* dloss, float* dhid, float* dw2, float* db2,
                         int G, int H, void* stream);
+/* ... + the caller's scratch: deterministic mode stores the per-16-sub-graph sums of dw2 / db2 (ceil(G / 16) (H + 1) floats) and adds
+ * them in chunk order */
+int subgc_gpn_score_bwd_ws(const float* hid, const uint8_t* keep, float keep_scale, const float* w2, const float* score,
+                           const float* dloss, float* dhid, float* dw2, float* db2, int G, int H, void* workspace, size_t ws_bytes,
+                           void* stream);
 
 /* sub-graph NMS by node-set IoU (replaces gpn.py:108-150, O(M^2) python sets).
  * score [M], idx int64 [M,N] (row stride idx_stride), len int32 [M] (valid prefix length).
@@ -318,6 +348,10 @@ int subgc_embed_fwd(const float* table, const int64_t* tok, int64_t tok_stride, 
 int subgc_embed_bwd(const float* table, const int64_t* tok, int64_t tok_stride, const uint8_t* keep,
                     float keep_scale, const float* dout, float* dtable, int n, int E, int vocab_rows,
                     void* stream);
+/* subgc_embed_bwd + the caller's scratch: deterministic mode needs (2 V + 4 (V + 1) + n) ints (16-byte rounded) + 2 ceil(n / 64) E floats
+ * (V = vocab_rows); with the mode off it is subgc_embed_bwd and ignores the workspace */
+int subgc_embed_bwd_ws(const float* table, const int64_t* tok, int64_t tok_stride, const uint8_t* keep, float keep_scale,
+                       const float* dout, float* dtable, int n, int E, int vocab_rows, void* workspace, size_t ws_bytes, void* stream);
 
 /* One LSTMCell step (AttModel.py:411, :423 -> nn.LSTMCell) for a decode batch of S <= 32 rows in ONE launch: the gate
  * GEMM x[S,K] . w_perm[4R,K]^T streams the weights through the matrix pipe and the cell update runs in its epilogue.
@@ -775,6 +809,10 @@ int subgc_copy2d_f32(const float* x, int64_t ldx, float* y, int64_t ldy, int row
 /* dX[rows[m], :] += src[m, :] for m < min(M, *m_dev) (fp32 atomics; negative rows skipped) */
 int subgc_scatter_add_rows(const float* src, int64_t lds, const int32_t* rows, float* dX, int64_t ldx,
                            int M, int L, const int32_t* m_dev, void* stream);
+/* subgc_scatter_add_rows + the caller's scratch; x_rows = rows of dX (deterministic mode skips ids outside [0, x_rows) as it skips
+ * negative ones).  Deterministic mode needs the layout of subgc_embed_bwd_ws with V = x_rows, n = M, E = L. */
+int subgc_scatter_add_rows_ws(const float* src, int64_t lds, const int32_t* rows, float* dX, int64_t ldx, int M, int L,
+                              const int32_t* m_dev, int x_rows, void* workspace, size_t ws_bytes, void* stream);
 
 /* fused global-norm clip + Adam over one flat fp32 bucket (misc/utils.py:174-200,234-235):
  * pass 1 accumulates sum(g^2) into *sumsq (caller zeroes it), pass 2 applies
@@ -784,6 +822,9 @@ int subgc_scatter_add_rows(const float* src, int64_t lds, const int32_t* rows, f
  * p_bf16 (optional, n elements): the bf16 snapshot of the updated weights, written in the same sweep (what the bf16-storage
  * GEMMs of BASELINE configs 3 / 5 read).                                                                                */
 int subgc_sumsq_f32(const float* g, int64_t n, float* sumsq, void* stream);
+/* ... + the caller's scratch: deterministic mode writes min(512, ceil(n / 1024)) workgroup partials (4 bytes each) and adds their
+ * ordered sum to *sumsq, so successive calls on one stream add in stream order */
+int subgc_sumsq_f32_ws(const float* g, int64_t n, float* sumsq, void* workspace, size_t ws_bytes, void* stream);
 int subgc_clip_adam_step(float* p, float* g, float* m, float* v, int64_t n, const float* sumsq,
                          float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
                          int step, float grad_scale, uint16_t* p_bf16, void* stream);

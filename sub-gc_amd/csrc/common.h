@@ -40,6 +40,19 @@ inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // gpn.py:117-118) instead of clamping or reading out of range.  One extra launch + a stream synchronisation per checked tensor: a
 // debugging aid, never on in the timed paths; inside a stream capture the checks are skipped (a synchronisation is illegal there).
 bool debug_bounds();
+// Deterministic mode (subgc_deterministic(1); off by default): every reduction of the training step sums in an order fixed by the
+// shape alone -- no float atomics, no alignment- or workspace-dependent plan.  The `_ws` entry points and the colsum / BatchNorm
+// paths read it when they enqueue; entry points without scratch that would add with atomics return SUBGC_EINVAL instead.
+bool deterministic();
+// det.hip: the deterministic forms (inverted index + fixed-order gather sums, slab partials + ordered finish passes)
+int det_embed_bwd(const float* table, const int64_t* tok, int64_t tok_stride, const uint8_t* keep, float keep_scale, const float* dout,
+                  float* dtable, int n, int E, int vocab_rows, void* workspace, size_t ws_bytes, hipStream_t s);
+int det_scatter_add_rows(const float* src, int64_t lds, const int32_t* rows, float* dX, int64_t ldx, int M, int L, const int32_t* m_dev,
+                         int x_rows, void* workspace, size_t ws_bytes, hipStream_t s);
+int det_pool_bwd(const float* dout, const int64_t* idx, int64_t idx_stride, const float* w, int64_t w_g, int64_t w_i, const float* denom,
+                 const int32_t* img, const int32_t* argmax, float* dX, int G, int N, int L, int x_rows, void* workspace, size_t ws_bytes,
+                 hipStream_t s);
+int det_sumsq(const float* g, int64_t n, float* sumsq, void* workspace, size_t ws_bytes, hipStream_t s);
 // every x[r * ld + c], r < rows, c < cols (elem = 4: int32, 8: int64) must lie in [lo, hi] or equal `also_ok` (pass lo - 1 for "nothing else")
 int debug_check_range(const void* x, int elem, int64_t rows, int64_t cols, int64_t ld, int64_t lo, int64_t hi, int64_t also_ok, const char* what,
                       hipStream_t s);

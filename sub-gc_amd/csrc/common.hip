@@ -88,6 +88,12 @@ int run_check(hipStream_t s, F&& launch, unsigned long long (&res)[2], const cha
 
 bool debug_bounds() { return g_debug_bounds.load(std::memory_order_relaxed) != 0; }
 
+// Deterministic mode: process-wide (NOT thread-local: the autograd backward runs on its own thread), read at enqueue time
+namespace {
+std::atomic<int> g_deterministic{0};
+}
+bool deterministic() { return g_deterministic.load(std::memory_order_relaxed) != 0; }
+
 int debug_check_range(const void* x, int elem, int64_t rows, int64_t cols, int64_t ld, int64_t lo, int64_t hi, int64_t also_ok, const char* what,
                       hipStream_t s) {
     if (!x || rows <= 0 || cols <= 0 || capturing(s)) return SUBGC_OK;
@@ -171,6 +177,10 @@ SUBGC_API const char* subgc_arch(void) { return "gfx950"; }
 
 SUBGC_API int subgc_debug_bounds(int on) {
     return subgc::g_debug_bounds.exchange(on ? 1 : 0);
+}
+
+SUBGC_API int subgc_deterministic(int on) {
+    return subgc::g_deterministic.exchange(on ? 1 : 0);
 }
 
 SUBGC_API int subgc_prof_enable(int family, int on) {

@@ -750,6 +750,7 @@ SUBGC_API int subgc_token_rows_f32(const float* table, int64_t ldt, const int64_
 SUBGC_API int subgc_embed_bwd(const float* table, const int64_t* tok, int64_t tok_stride, const uint8_t* keep, float keep_scale,
                               const float* dout, float* dtable, int n, int E, int vocab_rows, void* stream) {
     SUBGC_REQUIRE(n >= 0 && E > 0 && vocab_rows > 0, "embed_bwd: bad sizes");
+    SUBGC_REQUIRE(!subgc::deterministic(), "embed_bwd: adds with float atomics; in deterministic mode call subgc_embed_bwd_ws");
     if (n == 0) return SUBGC_OK;
     SUBGC_REQUIRE(table && tok && dout && dtable, "embed_bwd: null pointer");
     SUBGC_DEBUG_RANGE(tok, 8, n, 1, tok_stride, 0, vocab_rows - 1, -1, "embed_bwd: tok (word ids)", stream);
@@ -757,6 +758,15 @@ SUBGC_API int subgc_embed_bwd(const float* table, const int64_t* tok, int64_t to
     hipLaunchKernelGGL(embed_bwd_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, table, tok, tok_stride, keep, keep_scale, dout,
                        dtable, n, E, vocab_rows);
     return subgc::check_launch("subgc_embed_bwd");
+}
+SUBGC_API int subgc_embed_bwd_ws(const float* table, const int64_t* tok, int64_t tok_stride, const uint8_t* keep, float keep_scale,
+                                 const float* dout, float* dtable, int n, int E, int vocab_rows, void* workspace, size_t ws_bytes, void* stream) {
+    if (!subgc::deterministic()) return subgc_embed_bwd(table, tok, tok_stride, keep, keep_scale, dout, dtable, n, E, vocab_rows, stream);
+    SUBGC_REQUIRE(n >= 0 && E > 0 && vocab_rows > 0, "embed_bwd_ws: bad sizes");
+    if (n == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(table && tok && dout && dtable, "embed_bwd_ws: null pointer");
+    SUBGC_DEBUG_RANGE(tok, 8, n, 1, tok_stride, 0, vocab_rows - 1, -1, "embed_bwd_ws: tok (word ids)", stream);
+    return subgc::det_embed_bwd(table, tok, tok_stride, keep, keep_scale, dout, dtable, n, E, vocab_rows, workspace, ws_bytes, (hipStream_t)stream);
 }
 
 SUBGC_API int subgc_lstm_fwd(const float* g0, int64_t ld0, const float* g1, int64_t ld1, const float* g2, int64_t ld2, const float* b0,
@@ -1103,10 +1113,19 @@ SUBGC_API int subgc_copy2d_f32(const float* x, int64_t ldx, float* y, int64_t ld
 SUBGC_API int subgc_scatter_add_rows(const float* src, int64_t lds, const int32_t* rows, float* dX, int64_t ldx, int M, int L,
                                      const int32_t* m_dev, void* stream) {
     SUBGC_REQUIRE(M >= 0 && L > 0 && lds >= L && ldx >= L, "scatter_add_rows: bad sizes");
+    SUBGC_REQUIRE(!subgc::deterministic(), "scatter_add_rows: adds with float atomics; in deterministic mode call subgc_scatter_add_rows_ws");
     if (M == 0) return SUBGC_OK;
     SUBGC_REQUIRE(src && rows && dX, "scatter_add_rows: null pointer");
     hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(M), dim3(256), 0, (hipStream_t)stream, src, lds, rows, dX, ldx, M, L, m_dev);
     return subgc::check_launch("subgc_scatter_add_rows");
+}
+SUBGC_API int subgc_scatter_add_rows_ws(const float* src, int64_t lds, const int32_t* rows, float* dX, int64_t ldx, int M, int L,
+                                        const int32_t* m_dev, int x_rows, void* workspace, size_t ws_bytes, void* stream) {
+    if (!subgc::deterministic()) return subgc_scatter_add_rows(src, lds, rows, dX, ldx, M, L, m_dev, stream);
+    SUBGC_REQUIRE(M >= 0 && L > 0 && lds >= L && ldx >= L && x_rows > 0, "scatter_add_rows_ws: bad sizes");
+    if (M == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(src && rows && dX, "scatter_add_rows_ws: null pointer");
+    return subgc::det_scatter_add_rows(src, lds, rows, dX, ldx, M, L, m_dev, x_rows, workspace, ws_bytes, (hipStream_t)stream);
 }
 SUBGC_API int subgc_relu_bwd(const float* dy, const void* y, float scale, void* dz, int64_t n, int bf16_bits, void* stream) {
     SUBGC_REQUIRE(n >= 0, "relu_bwd: bad size");
@@ -1160,6 +1179,7 @@ SUBGC_API int subgc_gather_rows_multi_i64(int count, const float* s0, int64_t ld
 }
 SUBGC_API int subgc_sumsq_f32(const float* g, int64_t n, float* sumsq, void* stream) {
     SUBGC_REQUIRE(n >= 0, "sumsq: bad size");
+    SUBGC_REQUIRE(!subgc::deterministic(), "sumsq: adds with float atomics; in deterministic mode call subgc_sumsq_f32_ws");
     if (n == 0) return SUBGC_OK;
     SUBGC_REQUIRE(g && sumsq, "sumsq: null pointer");
     if (n % 4 == 0 && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
@@ -1170,6 +1190,13 @@ SUBGC_API int subgc_sumsq_f32(const float* g, int64_t n, float* sumsq, void* str
     }
     hipLaunchKernelGGL(sumsq_kernel, dim3(std::min(ew_grid(n), 1024)), dim3(256), 0, (hipStream_t)stream, g, n, sumsq);
     return subgc::check_launch("subgc_sumsq_f32");
+}
+SUBGC_API int subgc_sumsq_f32_ws(const float* g, int64_t n, float* sumsq, void* workspace, size_t ws_bytes, void* stream) {
+    if (!subgc::deterministic()) return subgc_sumsq_f32(g, n, sumsq, stream);
+    SUBGC_REQUIRE(n >= 0, "sumsq_ws: bad size");
+    if (n == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(g && sumsq, "sumsq_ws: null pointer");
+    return subgc::det_sumsq(g, n, sumsq, workspace, ws_bytes, (hipStream_t)stream);
 }
 namespace {
 template <bool ZERO>

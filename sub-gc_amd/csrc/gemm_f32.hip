@@ -1117,9 +1117,54 @@ __global__ void zero_kernel(float* p, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = 0.f;
 }
+// deterministic mode, any N / ld / alignment: a lane owns one column, and its sum runs in the order of colsum_vec_kernel / colsum_bf16_body
+// (wave w: rows r0 + w, r0 + w + 4, ...; the four waves added 0 + 1 + 2 + 3), stored to the slab's partial row
+template <bool B16>
+__global__ __launch_bounds__(256) void colsum_det_kernel(const void* __restrict__ Xv, int64_t ldx, int M, int N, const int32_t* m_dev,
+                                                         int rows_per_block, float* __restrict__ part) {
+    __shared__ float sm[4][64];
+    if (m_dev) M = min(M, *m_dev);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int col = blockIdx.x * 64 + lane;
+    const int r0 = blockIdx.y * rows_per_block, r1 = min(M, r0 + rows_per_block);
+    float acc = 0.f;
+    if (col < N)
+        for (int r = r0 + w; r < r1; r += 4)
+            acc += B16 ? subgc_bf2f(static_cast<const uint16_t*>(Xv)[(int64_t)r * ldx + col]) : static_cast<const float*>(Xv)[(int64_t)r * ldx + col];
+    sm[w][lane] = acc;
+    __syncthreads();
+    if (w == 0 && col < N) part[(int64_t)blockIdx.y * N + col] = sm[0][lane] + sm[1][lane] + sm[2][lane] + sm[3][lane];
+}
 }  // namespace
 
 namespace {
+// deterministic mode: slabs from the shape alone (the rows per slab of colsum_plan, every M, N), the partials always summed by the
+// ordered finish pass; float4 slab kernels where the alignment allows them, the one-column form otherwise -- the same sums either way
+int colsum_det(const void* X, int b16, int64_t ldx, int M, int N, float* out, int accumulate, const int32_t* m_dev, void* workspace,
+               size_t ws_bytes, hipStream_t s, const char* what) {
+    if (M == 0) {
+        if (!accumulate) hipLaunchKernelGGL(zero_kernel, dim3((N + 255) / 256), dim3(256), 0, s, out, N);
+        return subgc::check_launch(what);
+    }
+    const int col_groups = ((N + 3) / 4 + 63) / 64;
+    const int rpb = std::max(16, (int)(((int64_t)M * col_groups + 1023) / 1024));
+    const int slabs = (M + rpb - 1) / rpb;
+    const size_t need = (size_t)slabs * N * sizeof(float);
+    SUBGC_REQUIRE(workspace && ws_bytes >= need, "%s: deterministic mode needs %zu bytes of workspace (got %zu)", what, need,
+                  workspace ? ws_bytes : (size_t)0);
+    float* part = static_cast<float*>(workspace);
+    const bool wal = (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && N % 4 == 0 && ldx % 4 == 0;
+    if (!b16 && wal && aligned16(X))
+        hipLaunchKernelGGL(colsum_vec_kernel, dim3((N / 4 + 63) / 64, slabs), dim3(256), 0, s, static_cast<const float*>(X), ldx, M, N, out, m_dev, rpb, part);
+    else if (b16 && wal && (reinterpret_cast<uintptr_t>(X) & 7) == 0)
+        hipLaunchKernelGGL(colsum_bf16_kernel, dim3((N / 4 + 63) / 64, slabs), dim3(256), 0, s, static_cast<const uint16_t*>(X), ldx, M, N, out, m_dev, rpb, part);
+    else if (b16)
+        hipLaunchKernelGGL(colsum_det_kernel<true>, dim3((N + 63) / 64, slabs), dim3(256), 0, s, X, ldx, M, N, m_dev, rpb, part);
+    else
+        hipLaunchKernelGGL(colsum_det_kernel<false>, dim3((N + 63) / 64, slabs), dim3(256), 0, s, X, ldx, M, N, m_dev, rpb, part);
+    hipLaunchKernelGGL(colsum_finish_kernel, dim3((N + 63) / 64), dim3(256), 0, s, (const float*)part, slabs, N, out, accumulate);
+    return subgc::check_launch(what);
+}
 // slabs of the float4 column sums: with a workspace ~1024 workgroups of short slabs + one finishing pass; without, slabs of 256
 // rows merged by atomics
 struct ColsumPlan { int rows_per_block; int slabs; float* part; };
@@ -1139,6 +1184,7 @@ SUBGC_API int subgc_colsum_bf16(const uint16_t* X, int64_t ldx, int M, int N, fl
     if (N == 0) return SUBGC_OK;
     SUBGC_REQUIRE(X && out, "colsum_bf16: null pointer");
     hipStream_t s = (hipStream_t)stream;
+    if (subgc::deterministic()) return colsum_det(X, 1, ldx, M, N, out, accumulate, m_dev, workspace, ws_bytes, s, "subgc_colsum_bf16");
     const bool vec = N % 4 == 0 && ldx % 4 == 0 && (reinterpret_cast<uintptr_t>(X) & 7) == 0;
     const ColsumPlan pl = vec && M > 0 ? colsum_plan(M, N, workspace, ws_bytes) : ColsumPlan{256, (M + 255) / 256, nullptr};
     if (pl.part) {
@@ -1169,6 +1215,11 @@ SUBGC_API int subgc_colsum_bf16_set(int n, const uint16_t* X0, const uint16_t* X
     float* out[3] = {out0, out1, out2};
     for (int i = 0; i < n; ++i) SUBGC_REQUIRE(X[i] && out[i], "colsum_bf16_set: null pointer");
     hipStream_t s = (hipStream_t)stream;
+    if (subgc::deterministic()) {                 // one matrix at a time: each gets the bits of its own subgc_colsum_bf16 call
+        for (int i = 0; i < n; ++i)
+            if (int rc = subgc_colsum_bf16(X[i], ldx, M, N, out[i], accumulate, nullptr, workspace, ws_bytes, stream)) return rc;
+        return SUBGC_OK;
+    }
     bool vec = N % 4 == 0 && ldx % 4 == 0 && M > 0;
     for (int i = 0; i < n; ++i) vec = vec && (reinterpret_cast<uintptr_t>(X[i]) & 7) == 0;
     ColsumPlan pl = vec ? colsum_plan(M, N, workspace, ws_bytes / (size_t)n) : ColsumPlan{256, 0, nullptr};
@@ -1189,6 +1240,7 @@ SUBGC_API int subgc_colsum_f32(const float* X, int64_t ldx, int M, int N, float*
     if (N == 0) return SUBGC_OK;
     SUBGC_REQUIRE(X && out, "colsum: null pointer");
     hipStream_t s = (hipStream_t)stream;
+    if (subgc::deterministic()) return colsum_det(X, 0, ldx, M, N, out, accumulate, m_dev, workspace, ws_bytes, s, "subgc_colsum_f32");
     const bool vec = N % 4 == 0 && ldx % 4 == 0 && aligned16(X);
     const ColsumPlan pl = vec && M > 0 ? colsum_plan(M, N, workspace, ws_bytes) : ColsumPlan{256, (M + 255) / 256, nullptr};
     if (pl.part) {

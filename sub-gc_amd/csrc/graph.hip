@@ -623,6 +623,75 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
         dX[i] = gamma[c] * rstd[c] * (dY[i] - dbeta[c] * invM - xh * dgamma[c] * invM);
     }
 }
+// deterministic mode: the two column reductions in ONE source for every alignment -- VEC = a lane owns four adjacent columns (float4 loads),
+// otherwise one; each column's arithmetic is the same scalar code with contraction off (no FMA in either form), rows in the order wave w:
+// r0 + w, r0 + w + 4, ..., waves added 0 + 1 + 2 + 3; the slab sums go to the partials bn_finalize_kernel / bn_sum_slabs_kernel add in order
+template <bool VEC>
+__global__ __launch_bounds__(256) void bn_colsum_det_kernel(const float* __restrict__ X, int M, int C, const float* __restrict__ center, int square,
+                                                            int rows_per_block, float* __restrict__ part) {
+#pragma clang fp contract(off)
+    constexpr int V = VEC ? 4 : 1;
+    __shared__ float sm[4][64][V];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = (blockIdx.x * 64 + lane) * V;
+    const int r0 = blockIdx.y * rows_per_block, r1 = min(M, r0 + rows_per_block);
+    float acc[V], mu[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) { acc[k] = 0.f; mu[k] = (center && col < C) ? center[col + k] : 0.f; }
+    if (col < C)
+        for (int r = r0 + w; r < r1; r += 4) {
+            float x[V];
+            if (VEC) { const float4 t = *reinterpret_cast<const float4*>(X + (int64_t)r * C + col); x[0] = t.x; x[1 % V] = t.y; x[2 % V] = t.z; x[3 % V] = t.w; }
+            else x[0] = X[(int64_t)r * C + col];
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                const float d = x[k] - mu[k];
+                acc[k] = square ? acc[k] + d * d : acc[k] + d;
+            }
+        }
+#pragma unroll
+    for (int k = 0; k < V; ++k) sm[w][lane][k] = acc[k];
+    __syncthreads();
+    if (w == 0 && col < C)
+#pragma unroll
+        for (int k = 0; k < V; ++k) part[(int64_t)blockIdx.y * C + col + k] = sm[0][lane][k] + sm[1][lane][k] + sm[2][lane][k] + sm[3][lane][k];
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void bn_bwd_reduce_det_kernel(const float* __restrict__ dY, const float* __restrict__ X, int M, int C,
+                                                                const float* __restrict__ mean, const float* __restrict__ rstd, int rows_per_block,
+                                                                float* __restrict__ part) {
+#pragma clang fp contract(off)
+    constexpr int V = VEC ? 4 : 1;
+    __shared__ float sg[4][64][V], sb[4][64][V];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, col = (blockIdx.x * 64 + lane) * V;
+    const int r0 = blockIdx.y * rows_per_block, r1 = min(M, r0 + rows_per_block);
+    float ag[V], ab[V], mu[V], rs[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) { ag[k] = 0.f; ab[k] = 0.f; mu[k] = col < C ? mean[col + k] : 0.f; rs[k] = col < C ? rstd[col + k] : 0.f; }
+    if (col < C)
+        for (int r = r0 + w; r < r1; r += 4) {
+            float dy[V], x[V];
+            if (VEC) {
+                const float4 a = *reinterpret_cast<const float4*>(dY + (int64_t)r * C + col), b = *reinterpret_cast<const float4*>(X + (int64_t)r * C + col);
+                dy[0] = a.x; dy[1 % V] = a.y; dy[2 % V] = a.z; dy[3 % V] = a.w;
+                x[0] = b.x; x[1 % V] = b.y; x[2 % V] = b.z; x[3 % V] = b.w;
+            } else { dy[0] = dY[(int64_t)r * C + col]; x[0] = X[(int64_t)r * C + col]; }
+#pragma unroll
+            for (int k = 0; k < V; ++k) {
+                ab[k] = ab[k] + dy[k];
+                const float t = dy[k] * (x[k] - mu[k]);
+                ag[k] = ag[k] + t * rs[k];
+            }
+        }
+#pragma unroll
+    for (int k = 0; k < V; ++k) { sg[w][lane][k] = ag[k]; sb[w][lane][k] = ab[k]; }
+    __syncthreads();
+    if (w == 0 && col < C)
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            part[((int64_t)blockIdx.y * 2 + 0) * C + col + k] = sg[0][lane][k] + sg[1][lane][k] + sg[2][lane][k] + sg[3][lane][k];
+            part[((int64_t)blockIdx.y * 2 + 1) * C + col + k] = sb[0][lane][k] + sb[1][lane][k] + sb[2][lane][k] + sb[3][lane][k];
+        }
+}
 __global__ void zero_f32_kernel(float* p, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0.f;
 }
@@ -757,19 +826,30 @@ SUBGC_API int subgc_bn_fwd(const float* X, float* Y, int M, int C, const float* 
     SUBGC_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, "bn_fwd: workspace must be 16-byte aligned");
     SUBGC_REQUIRE(save_mean && save_rstd, "bn_fwd(train): save buffers required");
     const bool vec = bn_vec_ok(C, X, save_mean, save_rstd);
-    const int rpb = vec ? bn_rows_per_block(M, C) : 512;
+    const bool det = subgc::deterministic();         // slabs from the shape alone, always summed in order (no atomics)
+    const int rpb = vec || det ? bn_rows_per_block(M, C) : 512;
     dim3 g(vec ? (C + 255) / 256 : (C + 63) / 64, (M + rpb - 1) / rpb);
     float* part = vec && workspace && ws_bytes >= (size_t)g.y * C * sizeof(float) ? static_cast<float*>(workspace) : nullptr;
+    if (det) {
+        const size_t need = (size_t)g.y * C * sizeof(float);
+        SUBGC_REQUIRE(workspace && ws_bytes >= need, "subgc_bn_fwd: deterministic mode needs %zu bytes of workspace (got %zu)", need,
+                      workspace ? ws_bytes : (size_t)0);
+        part = static_cast<float*>(workspace);
+    }
     if (!part) {
         hipLaunchKernelGGL(zero_f32_kernel, dim3((C + 255) / 256), dim3(256), 0, s, save_mean, (int64_t)C);
         hipLaunchKernelGGL(zero_f32_kernel, dim3((C + 255) / 256), dim3(256), 0, s, save_rstd, (int64_t)C);
     }
-    if (vec) hipLaunchKernelGGL(bn_colsum_vec_kernel, g, dim3(256), 0, s, X, M, C, (const float*)nullptr, save_mean, 0, rpb, part);
+    if (det && vec) hipLaunchKernelGGL(bn_colsum_det_kernel<true>, g, dim3(256), 0, s, X, M, C, (const float*)nullptr, 0, rpb, part);
+    else if (det) hipLaunchKernelGGL(bn_colsum_det_kernel<false>, g, dim3(256), 0, s, X, M, C, (const float*)nullptr, 0, rpb, part);
+    else if (vec) hipLaunchKernelGGL(bn_colsum_vec_kernel, g, dim3(256), 0, s, X, M, C, (const float*)nullptr, save_mean, 0, rpb, part);
     else hipLaunchKernelGGL(bn_colsum_kernel, g, dim3(256), 0, s, X, M, C, (const float*)nullptr, save_mean, 0, rpb);
     const dim3 fg(part ? (C + 63) / 64 : (C + 255) / 256);
     hipLaunchKernelGGL(bn_finalize_kernel, fg, dim3(256), 0, s, save_mean, M, C, 0, save_mean, save_rstd,
                        running_mean, running_var, momentum, eps, (const float*)part, (int)g.y);
-    if (vec) hipLaunchKernelGGL(bn_colsum_vec_kernel, g, dim3(256), 0, s, X, M, C, (const float*)save_mean, save_rstd, 1, rpb, part);
+    if (det && vec) hipLaunchKernelGGL(bn_colsum_det_kernel<true>, g, dim3(256), 0, s, X, M, C, (const float*)save_mean, 1, rpb, part);
+    else if (det) hipLaunchKernelGGL(bn_colsum_det_kernel<false>, g, dim3(256), 0, s, X, M, C, (const float*)save_mean, 1, rpb, part);
+    else if (vec) hipLaunchKernelGGL(bn_colsum_vec_kernel, g, dim3(256), 0, s, X, M, C, (const float*)save_mean, save_rstd, 1, rpb, part);
     else hipLaunchKernelGGL(bn_colsum_kernel, g, dim3(256), 0, s, X, M, C, (const float*)save_mean, save_rstd, 1, rpb);
     hipLaunchKernelGGL(bn_finalize_kernel, fg, dim3(256), 0, s, save_rstd, M, C, 1, save_mean, save_rstd,
                        running_mean, running_var, momentum, eps, (const float*)part, (int)g.y);
@@ -784,15 +864,25 @@ SUBGC_API int subgc_bn_bwd(const float* dY, const float* X, const float* gamma, 
     SUBGC_REQUIRE(dY && X && gamma && save_mean && save_rstd && dX && dgamma && dbeta, "bn_bwd: null pointer");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)M * C;
-    const bool vec = bn_vec_ok(C, X, dY, save_mean) && bn_vec_ok(C, save_rstd, dgamma, dbeta);
-    const int rpb = vec ? bn_rows_per_block(M, C) : 512;
+    const bool det = subgc::deterministic();
+    const bool vec = bn_vec_ok(C, X, dY, save_mean) && bn_vec_ok(C, save_rstd, dgamma, dbeta) &&
+                     (!det || (reinterpret_cast<uintptr_t>(workspace) & 15) == 0);
+    const int rpb = vec || det ? bn_rows_per_block(M, C) : 512;
     dim3 g(vec ? (C + 255) / 256 : (C + 63) / 64, (M + rpb - 1) / rpb);
     float* part = vec && workspace && ws_bytes >= (size_t)g.y * 2 * C * sizeof(float) ? static_cast<float*>(workspace) : nullptr;
+    if (det) {
+        const size_t need = (size_t)g.y * 2 * C * sizeof(float);
+        SUBGC_REQUIRE(workspace && ws_bytes >= need, "subgc_bn_bwd: deterministic mode needs %zu bytes of workspace (got %zu)", need,
+                      workspace ? ws_bytes : (size_t)0);
+        part = static_cast<float*>(workspace);
+    }
     if (!part) {
         hipLaunchKernelGGL(zero_f32_kernel, dim3((C + 255) / 256), dim3(256), 0, s, dgamma, (int64_t)C);
         hipLaunchKernelGGL(zero_f32_kernel, dim3((C + 255) / 256), dim3(256), 0, s, dbeta, (int64_t)C);
     }
-    if (vec) hipLaunchKernelGGL(bn_bwd_reduce_vec_kernel, g, dim3(256), 0, s, dY, X, M, C, save_mean, save_rstd, dgamma, dbeta, rpb, part);
+    if (det && vec) hipLaunchKernelGGL(bn_bwd_reduce_det_kernel<true>, g, dim3(256), 0, s, dY, X, M, C, save_mean, save_rstd, rpb, part);
+    else if (det) hipLaunchKernelGGL(bn_bwd_reduce_det_kernel<false>, g, dim3(256), 0, s, dY, X, M, C, save_mean, save_rstd, rpb, part);
+    else if (vec) hipLaunchKernelGGL(bn_bwd_reduce_vec_kernel, g, dim3(256), 0, s, dY, X, M, C, save_mean, save_rstd, dgamma, dbeta, rpb, part);
     else hipLaunchKernelGGL(bn_bwd_reduce_kernel, g, dim3(256), 0, s, dY, X, M, C, save_mean, save_rstd, dgamma, dbeta, rpb);
     if (part) hipLaunchKernelGGL(bn_sum_slabs_kernel, dim3((C + 63) / 64), dim3(256), 0, s, (const float*)part, (int)g.y, C, dgamma, dbeta);
     const int ew_blocks = (int)std::min<int64_t>((total + 255) / 256, 4096);

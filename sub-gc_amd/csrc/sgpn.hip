@@ -135,6 +135,47 @@ __global__ void zero_kernel(float* p, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) p[i] = 0.f;
 }
+// deterministic mode: the same per-chunk sums as score_bwd_kernel, stored to part[chunk][H + 1] (dw2 columns, then db2) instead of added
+// with atomics; score_bwd_finish_kernel adds the chunks in chunk order
+__global__ __launch_bounds__(256) void score_bwd_det_kernel(const float* __restrict__ hid, const uint8_t* __restrict__ keep, float scale,
+                                                            const float* __restrict__ w2, const float* __restrict__ score,
+                                                            const float* __restrict__ dloss, float* __restrict__ dhid,
+                                                            float* __restrict__ part, int G, int H) {
+    __shared__ float dz_s[SB_CHUNK];
+    const int g0 = blockIdx.x * SB_CHUNK, n = min(SB_CHUNK, G - g0);
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        const int g = g0 + i;
+        const float s = score[g], t = g < G / 2 ? 1.f : 0.f;
+        dz_s[i] = dloss[0] * (s - t) / fmaxf((1.f - s) * s, 1e-12f) / (float)G * (s * (1.f - s));
+    }
+    __syncthreads();
+    float* __restrict__ row = part + (int64_t)blockIdx.x * (H + 1);
+    for (int h = threadIdx.x; h < H; h += blockDim.x) {
+        const float w = w2[h];
+        float acc = 0.f;
+        for (int i = 0; i < n; ++i) {
+            const int64_t q = (int64_t)(g0 + i) * H + h;
+            const float k = keep ? (keep[q] ? scale : 0.f) : 1.f;
+            dhid[q] = dz_s[i] * w * k;
+            acc += dz_s[i] * hid[q] * k;
+        }
+        row[h] = acc;
+    }
+    if (threadIdx.x == 0) {
+        float sum = 0.f;
+        for (int i = 0; i < n; ++i) sum += dz_s[i];
+        row[H] = sum;
+    }
+}
+__global__ __launch_bounds__(256) void score_bwd_finish_kernel(const float* __restrict__ part, int chunks, int H, float* __restrict__ dw2,
+                                                               float* __restrict__ db2) {
+    const int h = blockIdx.x * blockDim.x + threadIdx.x;
+    if (h > H) return;
+    float s = 0.f;
+    for (int c = 0; c < chunks; ++c) s += part[(int64_t)c * (H + 1) + h];
+    if (h < H) dw2[h] = s;
+    else db2[0] = s;
+}
 
 // ------------------------------------------------------------------ NMS
 constexpr int W = SUBGC_NMS_WORDS;
@@ -229,12 +270,26 @@ SUBGC_API int subgc_subgraph_pool_bwd(const float* dout, const int64_t* idx, int
     SUBGC_REQUIRE(G >= 0 && N > 0 && N <= MAXN && L > 0, "subgraph_pool_bwd: bad sizes");
     if (G == 0) return SUBGC_OK;
     SUBGC_REQUIRE(dout && idx && w && denom && img && argmax && dX, "subgraph_pool_bwd: null pointer");
+    SUBGC_REQUIRE(!subgc::deterministic(), "subgraph_pool_bwd: adds with float atomics; in deterministic mode call subgc_subgraph_pool_bwd_ws");
     SUBGC_DEBUG_RANGE(idx, 8, G, N, idx_stride, 0, N - 1, -1, "subgraph_pool_bwd: idx", stream);
     hipStream_t s = (hipStream_t)stream;
     subgc::ProfScope prof(SUBGC_FAM_POOL, s, 4.0 * G * L * 3.0);
     hipLaunchKernelGGL(pool_bwd_kernel, dim3((L + 255) / 256, G), dim3(256), 0, s, dout, idx, idx_stride, w, w_gstride, w_istride,
                        denom, img, argmax, dX, G, N, L);
     return subgc::check_launch("subgc_subgraph_pool_bwd");
+}
+SUBGC_API int subgc_subgraph_pool_bwd_ws(const float* dout, const int64_t* idx, int64_t idx_stride, const float* w, int64_t w_gstride,
+                                         int64_t w_istride, const float* denom, const int32_t* img, const int32_t* argmax, float* dX,
+                                         int G, int N, int L, int x_rows, void* workspace, size_t ws_bytes, void* stream) {
+    if (!subgc::deterministic())
+        return subgc_subgraph_pool_bwd(dout, idx, idx_stride, w, w_gstride, w_istride, denom, img, argmax, dX, G, N, L, stream);
+    SUBGC_REQUIRE(G >= 0 && N > 0 && N <= MAXN && L > 0 && x_rows > 0, "subgraph_pool_bwd_ws: bad sizes");
+    if (G == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(dout && idx && w && denom && img && argmax && dX, "subgraph_pool_bwd_ws: null pointer");
+    SUBGC_DEBUG_RANGE(idx, 8, G, N, idx_stride, 0, N - 1, -1, "subgraph_pool_bwd_ws: idx", stream);
+    hipStream_t s = (hipStream_t)stream;
+    subgc::ProfScope prof(SUBGC_FAM_POOL, s, 4.0 * G * L * 3.0);
+    return subgc::det_pool_bwd(dout, idx, idx_stride, w, w_gstride, w_istride, denom, img, argmax, dX, G, N, L, x_rows, workspace, ws_bytes, s);
 }
 
 SUBGC_API int subgc_gpn_score_fwd(const float* hid, const uint8_t* keep, float keep_scale, const float* w2, const float* b2,
@@ -252,12 +307,29 @@ SUBGC_API int subgc_gpn_score_bwd(const float* hid, const uint8_t* keep, float k
                                   const float* dloss, float* dhid, float* dw2, float* db2, int G, int H, void* stream) {
     SUBGC_REQUIRE(G > 0 && H > 0, "gpn_score_bwd: bad sizes");
     SUBGC_REQUIRE(hid && w2 && score && dloss && dhid && dw2 && db2, "gpn_score_bwd: null pointer");
+    SUBGC_REQUIRE(!subgc::deterministic(), "gpn_score_bwd: adds with float atomics; in deterministic mode call subgc_gpn_score_bwd_ws");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(zero_kernel, dim3((H + 255) / 256), dim3(256), 0, s, dw2, H);
     hipLaunchKernelGGL(zero_kernel, dim3(1), dim3(64), 0, s, db2, 1);
     hipLaunchKernelGGL(score_bwd_kernel, dim3((G + SB_CHUNK - 1) / SB_CHUNK), dim3(256), 0, s, hid, keep, keep_scale, w2, score, dloss, dhid, dw2, db2,
                        G, H);
     return subgc::check_launch("subgc_gpn_score_bwd");
+}
+SUBGC_API int subgc_gpn_score_bwd_ws(const float* hid, const uint8_t* keep, float keep_scale, const float* w2, const float* score,
+                                     const float* dloss, float* dhid, float* dw2, float* db2, int G, int H, void* workspace, size_t ws_bytes,
+                                     void* stream) {
+    if (!subgc::deterministic()) return subgc_gpn_score_bwd(hid, keep, keep_scale, w2, score, dloss, dhid, dw2, db2, G, H, stream);
+    SUBGC_REQUIRE(G > 0 && H > 0, "gpn_score_bwd_ws: bad sizes");
+    SUBGC_REQUIRE(hid && w2 && score && dloss && dhid && dw2 && db2, "gpn_score_bwd_ws: null pointer");
+    const int chunks = (G + SB_CHUNK - 1) / SB_CHUNK;
+    const size_t need = (size_t)chunks * (H + 1) * sizeof(float);
+    SUBGC_REQUIRE(workspace && ws_bytes >= need, "subgc_gpn_score_bwd_ws: deterministic mode needs %zu bytes of workspace (got %zu)", need,
+                  workspace ? ws_bytes : (size_t)0);
+    hipStream_t s = (hipStream_t)stream;
+    float* part = static_cast<float*>(workspace);
+    hipLaunchKernelGGL(score_bwd_det_kernel, dim3(chunks), dim3(256), 0, s, hid, keep, keep_scale, w2, score, dloss, dhid, part, G, H);
+    hipLaunchKernelGGL(score_bwd_finish_kernel, dim3((H + 1 + 255) / 256), dim3(256), 0, s, (const float*)part, chunks, H, dw2, db2);
+    return subgc::check_launch("subgc_gpn_score_bwd_ws");
 }
 
 SUBGC_API int subgc_subgraph_nms(const float* score, const int64_t* idx, int64_t idx_stride, const int32_t* len, int M, int N,

@@ -56,6 +56,10 @@ def setup(opt):
     and, when `opt.start_from` is set, resume its weights from `<start_from>/model.pth`."""
     if opt.caption_model != "topdown":
         raise Exception("Caption model not supported: {}".format(opt.caption_model))
+    if getattr(opt, "deterministic", 0):
+        # the reference's drivers fix their seeds and set cudnn.deterministic; here the library's fixed-order reductions (process-wide)
+        from .. import ops
+        ops.set_deterministic(True)
     model = TopDownModel(opt)
     start = vars(opt).get("start_from", None)
     if start is not None:

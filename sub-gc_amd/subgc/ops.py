@@ -154,6 +154,41 @@ class debug_bounds:
         lib().subgc_debug_bounds(int(self.prev))
 
 
+_DET = [False]         # mirror of subgc_deterministic as set through this module: the `_ws` wrappers hand over scratch only while it is on
+
+
+def set_deterministic(on):
+    """Switch the library's deterministic mode (subgc_deterministic) on or off for the whole process; returns the previous setting."""
+    prev = bool(lib().subgc_deterministic(int(bool(on))))
+    _DET[0] = bool(on)
+    return prev
+
+
+def _det_ws(t):
+    """`workspace, ws_bytes` of the `_ws` siblings: the current stream's scratch in deterministic mode; (NULL, 0) otherwise, where the
+    siblings launch their originals (no per-stream workspace is allocated for them, e.g. on the reducer's side stream)."""
+    return _ws(t) if _DET[0] else (None, 0)
+
+
+class deterministic:
+    """`with ops.deterministic(): ...` -- the library's deterministic mode (subgc_deterministic): every reduction of the training step sums
+    in an order fixed by the shape alone (inverted-index gather sums, slab partials with ordered finish passes; no float atomics), so two
+    runs from the same weights, batches and seeds give the same bits.  Process-wide, read when a call is enqueued; the previous setting
+    is restored on exit."""
+
+    def __init__(self, on=True):
+        self.on = bool(on)
+
+    def __enter__(self):
+        self.prev = lib().subgc_deterministic(int(self.on))
+        _DET[0] = self.on
+        return self
+
+    def __exit__(self, *exc):
+        lib().subgc_deterministic(int(self.prev))
+        _DET[0] = bool(self.prev)
+
+
 class gemm_tune:
     """Measurement-script switches of the GEMM dispatch, handed over per call in `flags` (the library keeps no tunable state):
     `with ops.gemm_tune(no_splitk=True, no_skinny=True): ...` for subgc_gemm_f32, `tile=128|256|"p8"`, `no_p8`, `splits=n` for subgc_gemm_bf16."""
@@ -615,8 +650,8 @@ def pool_fwd(X, idx, idx_stride, w, w_g, w_i, denom, img, G, N, L, want_argmax=T
 
 def pool_bwd(dout, idx, idx_stride, w, w_g, w_i, denom, img, am, dX, G, N, L):
     _pool_account(denom, G, L, False)
-    call("subgc_subgraph_pool_bwd", _ptr(dout), _ptr(idx, torch.int64), idx_stride, _ptr(w), w_g, w_i, _ptr(denom),
-         _ptr(img, torch.int32), _ptr(am, torch.int32), _ptr(dX), G, N, L, _stream())
+    call("subgc_subgraph_pool_bwd_ws", _ptr(dout), _ptr(idx, torch.int64), idx_stride, _ptr(w), w_g, w_i, _ptr(denom),
+         _ptr(img, torch.int32), _ptr(am, torch.int32), _ptr(dX), G, N, L, dX.size(0), *_det_ws(dX), _stream())
     return dX
 
 
@@ -633,8 +668,8 @@ def gpn_score_bwd(hid, keep, scale, w2, score, dloss):
     dhid = torch.empty_like(hid)
     dw2 = torch.empty(1, H, device=hid.device, dtype=torch.float32)
     db2 = torch.empty(1, device=hid.device, dtype=torch.float32)
-    call("subgc_gpn_score_bwd", _ptr(hid), _ptr(keep, torch.uint8), float(scale), _ptr(w2), _ptr(score), _ptr(dloss), _ptr(dhid),
-         _ptr(dw2), _ptr(db2), G, H, _stream())
+    call("subgc_gpn_score_bwd_ws", _ptr(hid), _ptr(keep, torch.uint8), float(scale), _ptr(w2), _ptr(score), _ptr(dloss), _ptr(dhid),
+         _ptr(dw2), _ptr(db2), G, H, *_det_ws(hid), _stream())
     return dhid, dw2, db2
 
 
@@ -916,8 +951,8 @@ def pick_lse_finish(lse_part, V, counts, seqlp):
 
 def embed_bwd(table, tok, tok_stride, keep, scale, dout, dtable):
     n, E = dout.shape
-    call("subgc_embed_bwd", _ptr(table), _ptr(tok, torch.int64), tok_stride, _ptr(keep, torch.uint8), float(scale), _ptr(dout),
-         _ptr(dtable), n, E, table.size(0), _stream())
+    call("subgc_embed_bwd_ws", _ptr(table), _ptr(tok, torch.int64), tok_stride, _ptr(keep, torch.uint8), float(scale), _ptr(dout),
+         _ptr(dtable), n, E, table.size(0), *_det_ws(dout), _stream())
     return dtable
 
 
@@ -1526,13 +1561,13 @@ def gather_rows_multi(pairs, rows):
 
 
 def scatter_add_rows(src, rows, dX, m_dev=None):
-    call("subgc_scatter_add_rows", _ptr(src), ld(src), _ptr(rows, torch.int32), _ptr(dX), ld(dX), src.size(0), src.size(1),
-         _ptr(m_dev, torch.int32), _stream())
+    call("subgc_scatter_add_rows_ws", _ptr(src), ld(src), _ptr(rows, torch.int32), _ptr(dX), ld(dX), src.size(0), src.size(1),
+         _ptr(m_dev, torch.int32), dX.size(0), *_det_ws(src), _stream())
     return dX
 
 
 def sumsq(g, out):
-    call("subgc_sumsq_f32", _ptr(g), g.numel(), _ptr(out), _stream())
+    call("subgc_sumsq_f32_ws", _ptr(g), g.numel(), _ptr(out), *_det_ws(g), _stream())
     return out
 
 
