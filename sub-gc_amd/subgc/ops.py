@@ -903,6 +903,15 @@ def lstm_step_skinny(x, w_perm, c_prev, c, hs, b0=None, b1=None, add1=None, tok=
          _ptr(c_prev, torch.float32), _ptr(c, torch.float32), *hp, int(is_b16(w_perm)), _stream())
 
 
+def gemm_skinny_wb16(x, W16, out, bias=None, relu=False):
+    """out = act(x W16^T + bias) for <= 16 fp32 rows against a bf16-STORED weight matrix, fp32 accumulation (subgc_gemm_skinny_wb16:
+    the h2att and logit products of a bf16 decode step)."""
+    M, K = x.shape
+    call("subgc_gemm_skinny_wb16", _ptr(x, torch.float32), ld(x), _ptr(W16, BF16), ld(W16), _ptr(out, torch.float32), ld(out),
+         _ptr(bias, torch.float32), M, W16.size(0), K, int(relu), _stream())
+    return out
+
+
 PICK_BEST_ELEMS = 16 * 8 * 16       # uint64 slots of one `best` buffer of the fused greedy pick (subgc_hip.h)
 
 

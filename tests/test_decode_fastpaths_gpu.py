@@ -61,18 +61,20 @@ def test_decode_with_and_without_the_table(golden, name, monkeypatch):
     np.testing.assert_array_equal(with_tab[0].cpu().numpy(), g.group("out")["seq"])
 
 
-def test_cached_decode_state_follows_load_state_dict(golden):
-    """The one-image decode replays a captured hipGraph holding weight snapshots: new weights must retire it."""
+@pytest.mark.parametrize("compute_dtype", ["fp32", "bf16"])
+def test_cached_decode_state_follows_load_state_dict(golden, compute_dtype):
+    """The one-image decode replays a captured hipGraph holding weight snapshots: new weights must retire it (under bf16 also the bf16
+    flat copy and the row-permuted bf16 LSTM snapshot the step streams)."""
     g = golden("subgc_greedy")
     w = golden("subgc_train").group("weights")
-    m = build(g, w, False)
+    m = build(g, w, False, compute_dtype=compute_dtype)
     b = {k: v.to(DEV) for k, v in g.tensors("inputs").items()}
     opt = g.meta["sample_opt"]
     first = m(*synthetic.sample_args(b), opt=opt, mode="sample")
     w2 = {k: (v * (0.5 if k.startswith(("core.", "embed.")) else 1.0)).astype(v.dtype) for k, v in w.items()}
     m.load_state_dict({k: torch.from_numpy(v) for k, v in w2.items()})
     again = m(*synthetic.sample_args(b), opt=opt, mode="sample")
-    fresh = build(g, w2, False)(*synthetic.sample_args(b), opt=opt, mode="sample")
+    fresh = build(g, w2, False, compute_dtype=compute_dtype)(*synthetic.sample_args(b), opt=opt, mode="sample")
     assert torch.equal(again[0], fresh[0])
     torch.testing.assert_close(again[1], fresh[1], atol=1e-5, rtol=1e-5)
     assert not torch.allclose(first[1], again[1])
@@ -239,14 +241,16 @@ def test_clip_adam_grad_scale_equals_scaling_first(n):
         torch.testing.assert_close(a, b, atol=1e-6, rtol=1e-5)
 
 
+@pytest.mark.parametrize("compute_dtype", ["fp32", "bf16"])
 @pytest.mark.parametrize("opt_over", [dict(sample_max=1, beam_size=1), dict(sample_max=1, beam_size=2)])
-def test_decode_after_the_fused_optimizer_step_uses_the_new_weights(golden, opt_over):
+def test_decode_after_the_fused_optimizer_step_uses_the_new_weights(golden, opt_over, compute_dtype):
     """train -> eval -> train -> eval: `parallel.FlatAdam.step` writes the weights through raw device pointers (no torch
     version counter moves), so it has to retire the decode-time snapshots itself (x->gates table, K-concatenated LSTM
-    matrices, captured hipGraphs); a second decode must equal a freshly built model holding the updated weights."""
+    matrices, captured hipGraphs; under bf16 also the bf16 flat copy it writes itself and the bf16 LSTM snapshot); a second
+    decode must equal a freshly built model holding the updated weights."""
     from subgc import parallel
     g = golden("subgc_greedy")
-    m = build(g, golden("subgc_train").group("weights"), False)
+    m = build(g, golden("subgc_train").group("weights"), False, compute_dtype=compute_dtype)
     b = {k: v.to(DEV) for k, v in g.tensors("inputs").items()}
     opt = dict(g.meta["sample_opt"], **opt_over)
     first = m(*synthetic.sample_args(b), opt=opt, mode="sample")
@@ -256,7 +260,7 @@ def test_decode_after_the_fused_optimizer_step_uses_the_new_weights(golden, opt_
     adam.step()
     again = m(*synthetic.sample_args(b), opt=opt, mode="sample")
     w2 = {k: v.detach().cpu().numpy().copy() for k, v in m.state_dict().items()}
-    fresh = build(g, w2, False)(*synthetic.sample_args(b), opt=opt, mode="sample")
+    fresh = build(g, w2, False, compute_dtype=compute_dtype)(*synthetic.sample_args(b), opt=opt, mode="sample")
     assert torch.equal(again[0], fresh[0])
     torch.testing.assert_close(again[1], fresh[1], atol=1e-5, rtol=1e-5)
     assert not torch.allclose(first[1], again[1])
@@ -326,7 +330,10 @@ def test_no_garbage_collection_inside_a_graph_capture(golden):
 
 
 @pytest.mark.parametrize("S,R,V,K1,K2,wb16", [(10, 1000, 9488, 1000, 2000, False), (16, 48, 150, 96, 144, False), (1, 52, 1003, 100, 104, False),
-                                              (10, 1000, 9488, 1000, 2000, True), (7, 48, 77, 96, 48, True)])
+                                              (10, 1000, 9488, 1000, 2000, True), (7, 48, 77, 96, 48, True),
+                                              # bf16 weights: one and sixteen rows, V % 16 != 0, K1 % 8 == 4 (8-byte aligned bf16 logit rows)
+                                              (1, 52, 1003, 100, 104, True), (16, 48, 7001, 52, 144, True), (16, 1000, 1003, 1004, 2000, True),
+                                              (1, 1000, 7001, 1004, 3000, True)])
 def test_dual_weight_stream_and_cell_pick_kernels(S, R, V, K1, K2, wb16):
     """Round 6's greedy step, kernel by kernel against torch: subgc_skinny_dual = [logits with the arg-max / log-sum-exp epilogue | a
     gate product in the permuted row order, written gate-major], then subgc_lstm_cell_pick = the attention LSTM's cell whose word is
