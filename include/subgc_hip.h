@@ -3,7 +3,7 @@
  *
  * The reference (YiwuZhong/Sub-GC) has no FFI layer: its hot path is ATen calls made from
  * models/AttModel.py, models/lib/{gcn_backbone,graph_conv,graph_conv_unit,gpn}.py and
- * misc/utils.py.  Each entry point below replaces the op site cited next to it (file:line in
+ * misc/utils.py.  Each of the 128 entry points below replaces the op site cited next to it (file:line in
  * /root/reference).  INTEGRATION.md shows the ctypes binding a maintainer adds.
  *
  * Contract for EVERY function:
@@ -833,6 +833,34 @@ int subgc_clip_adam_step(float* p, float* g, float* m, float* v, int64_t n, cons
 int subgc_clip_adam_step_zero(float* p, float* g, float* m, float* v, int64_t n, const float* sumsq,
                               float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
                               int step, float grad_scale, uint16_t* p_bf16, void* stream);
+
+/* fused global-norm clip + any optimizer rule of misc/utils.py:223-239 (build_optimizer, train.py:100; clip train.py:163) over one
+ * flat fp32 bucket: the sweep of subgc_clip_adam_step with the update rule as a parameter.  g *= grad_scale, then the clip coefficient
+ * from *sumsq (misc/utils.py:193), then the rule, element by element in the order of the torch class's single-tensor path:
+ *   SUBGC_OPTIM_ADAM     torch.optim.Adam (L2 decay added to g)       h0 = beta1, h1 = beta2     s1 = exp_avg, s2 = exp_avg_sq
+ *                        (the arithmetic of subgc_clip_adam_step)
+ *   SUBGC_OPTIM_ADAMW    torch.optim.AdamW (p *= 1 - lr wd first)     h0 = beta1, h1 = beta2     s1 = exp_avg, s2 = exp_avg_sq
+ *   SUBGC_OPTIM_SGD      torch.optim.SGD                              h0 = momentum, h1 = dampening    s1 = momentum_buffer (NULL
+ *                        when momentum == 0); flags bit 0: nesterov, bit 1: first step of the buffer (buffer = g, as torch clones it)
+ *   SUBGC_OPTIM_RMSPROP  torch.optim.RMSprop (momentum 0, uncentered) h0 = alpha                 s1 = square_avg
+ *   SUBGC_OPTIM_ADAGRAD  torch.optim.Adagrad (dense)                  h0 = lr_decay              s1 = sum
+ * `step` (>= 1) is the step count AFTER this step (Adam bias corrections, Adagrad's lr decay).  s2 may be NULL except for Adam / AdamW.
+ * `live` (device, 2 * n_live int64 element offsets lo0, hi0, lo1, hi1, ... ascending; NULL with n_live = 0: everything live): only the
+ * elements of these [lo, hi) ranges are updated.  The others -- parameters torch SKIPS because their .grad is None -- keep weight,
+ * state and (unless the `_zero` form zeroes it) gradient.  p_bf16 (optional): the bf16 snapshot, written in the same sweep.
+ * Elementwise, no atomics: deterministic mode changes nothing.  Invalid arguments return SUBGC_EINVAL before any launch.        */
+#define SUBGC_OPTIM_ADAM 0
+#define SUBGC_OPTIM_ADAMW 1
+#define SUBGC_OPTIM_SGD 2
+#define SUBGC_OPTIM_RMSPROP 3
+#define SUBGC_OPTIM_ADAGRAD 4
+int subgc_clip_optim_step(int rule, float* p, float* g, float* s1, float* s2, int64_t n, const int64_t* live, int n_live,
+                          const float* sumsq, float max_norm, float grad_scale, float lr, float h0, float h1, float eps,
+                          float weight_decay, int step, int flags, uint16_t* p_bf16, void* stream);
+/* ... with optimizer.zero_grad() folded in: g is left ZEROED over the whole bucket, skipped ranges included                      */
+int subgc_clip_optim_step_zero(int rule, float* p, float* g, float* s1, float* s2, int64_t n, const int64_t* live, int n_live,
+                               const float* sumsq, float max_norm, float grad_scale, float lr, float h0, float h1, float eps,
+                               float weight_decay, int step, int flags, uint16_t* p_bf16, void* stream);
 
 /* ======================================================================================
  * The teacher-forced recurrence as ONE call per direction (AttModel.py:157-175: the T-step loop around TopDownCore, :400-431).

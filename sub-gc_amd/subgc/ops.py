@@ -1583,3 +1583,19 @@ def sumsq(g, out):
 def clip_adam_step(p, g, m, v, sumsq_t, max_norm, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, p_bf16=None, zero_grad=False):
     call("subgc_clip_adam_step_zero" if zero_grad else "subgc_clip_adam_step", _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(sumsq_t), float(max_norm), float(lr),
          float(beta1), float(beta2), float(eps), float(wd), int(step), float(grad_scale), _ptr(p_bf16, BF16), _stream())
+
+
+OPTIM_RULES = {"adam": 0, "adamw": 1, "sgd": 2, "rmsprop": 3, "adagrad": 4}      # SUBGC_OPTIM_* of the header
+
+
+def clip_optim_step(rule, p, g, s1, s2, live, sumsq_t, max_norm, grad_scale, lr, h0, h1, eps, wd, step, nesterov=False, first=False,
+                    p_bf16=None, zero_grad=False):
+    """subgc_clip_optim_step(_zero): global-norm clip + one `rule` update over the flat bucket.  `live`: int64 device tensor of
+    [lo, hi) element ranges (flattened lo0, hi0, lo1, ...) of the parameters that are updated, or None for all of them."""
+    if live is not None and (live.dtype != torch.int64 or live.numel() % 2 or not live.is_contiguous()):
+        raise SubgcError("clip_optim_step: live must be a contiguous int64 tensor of [lo, hi) pairs")
+    if any(t is not None and (t.numel() < p.numel() or not t.is_contiguous()) for t in (p, g, s1, s2, p_bf16)):
+        raise SubgcError("clip_optim_step: p, g, the states and the snapshot must be contiguous with p.numel() elements")
+    call("subgc_clip_optim_step_zero" if zero_grad else "subgc_clip_optim_step", OPTIM_RULES[rule], _ptr(p), _ptr(g), _ptr(s1), _ptr(s2),
+         p.numel(), _ptr(live), 0 if live is None else live.numel() // 2, _ptr(sumsq_t), float(max_norm), float(grad_scale), float(lr),
+         float(h0), float(h1), float(eps), float(wd), int(step), (1 if nesterov else 0) | (2 if first else 0), _ptr(p_bf16, BF16), _stream())
