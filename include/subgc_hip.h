@@ -814,31 +814,19 @@ int subgc_scatter_add_rows(const float* src, int64_t lds, const int32_t* rows, f
 int subgc_scatter_add_rows_ws(const float* src, int64_t lds, const int32_t* rows, float* dX, int64_t ldx, int M, int L,
                               const int32_t* m_dev, int x_rows, void* workspace, size_t ws_bytes, void* stream);
 
-/* fused global-norm clip + Adam over one flat fp32 bucket (misc/utils.py:174-200,234-235):
- * pass 1 accumulates sum(g^2) into *sumsq (caller zeroes it), pass 2 applies
- * g *= max_norm / max(sqrt(sumsq), max_norm) (utils.py:193) and the torch.optim.Adam update.  grad_scale (1 for one GPU,
- * 1/world after a SUM all-reduce: DataParallel's mean of the replica losses, train.py:154-156) multiplies g first -- norm and
- * update see the averaged gradient without a separate pass over the bucket; g is left scaled and clipped.
- * p_bf16 (optional, n elements): the bf16 snapshot of the updated weights, written in the same sweep (what the bf16-storage
- * GEMMs of BASELINE configs 3 / 5 read).                                                                                */
+/* squared gradient norm for the global-norm clip (misc/utils.py:174-200): *sumsq += sum(g^2), the caller zeroes it.  The sweep below
+ * consumes it.                                                                                                            */
 int subgc_sumsq_f32(const float* g, int64_t n, float* sumsq, void* stream);
 /* ... + the caller's scratch: deterministic mode writes min(512, ceil(n / 1024)) workgroup partials (4 bytes each) and adds their
  * ordered sum to *sumsq, so successive calls on one stream add in stream order */
 int subgc_sumsq_f32_ws(const float* g, int64_t n, float* sumsq, void* workspace, size_t ws_bytes, void* stream);
-int subgc_clip_adam_step(float* p, float* g, float* m, float* v, int64_t n, const float* sumsq,
-                         float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
-                         int step, float grad_scale, uint16_t* p_bf16, void* stream);
-/* the same sweep with `optimizer.zero_grad()` (train.py calls it once per iteration) folded in: g is left ZEROED
- * instead of scaled and clipped, so the next iteration needs no fill pass over the gradient buffer.             */
-int subgc_clip_adam_step_zero(float* p, float* g, float* m, float* v, int64_t n, const float* sumsq,
-                              float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay,
-                              int step, float grad_scale, uint16_t* p_bf16, void* stream);
 
 /* fused global-norm clip + any optimizer rule of misc/utils.py:223-239 (build_optimizer, train.py:100; clip train.py:163) over one
- * flat fp32 bucket: the sweep of subgc_clip_adam_step with the update rule as a parameter.  g *= grad_scale, then the clip coefficient
- * from *sumsq (misc/utils.py:193), then the rule, element by element in the order of the torch class's single-tensor path:
+ * flat fp32 bucket, in ONE sweep.  g *= grad_scale (1 for one GPU, 1/world after a SUM all-reduce: DataParallel's mean of the replica
+ * losses, train.py:154-156 -- norm and update see the averaged gradient without a separate pass over the bucket), then the clip
+ * coefficient g *= max_norm / max(sqrt(*sumsq) * grad_scale, max_norm) (misc/utils.py:193), then the rule, element by element in the
+ * order of the torch class's single-tensor path; g is left scaled and clipped:
  *   SUBGC_OPTIM_ADAM     torch.optim.Adam (L2 decay added to g)       h0 = beta1, h1 = beta2     s1 = exp_avg, s2 = exp_avg_sq
- *                        (the arithmetic of subgc_clip_adam_step)
  *   SUBGC_OPTIM_ADAMW    torch.optim.AdamW (p *= 1 - lr wd first)     h0 = beta1, h1 = beta2     s1 = exp_avg, s2 = exp_avg_sq
  *   SUBGC_OPTIM_SGD      torch.optim.SGD                              h0 = momentum, h1 = dampening    s1 = momentum_buffer (NULL
  *                        when momentum == 0); flags bit 0: nesterov, bit 1: first step of the buffer (buffer = g, as torch clones it)

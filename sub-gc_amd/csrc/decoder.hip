@@ -638,80 +638,6 @@ __global__ __launch_bounds__(256) void gather_rows_multi_kernel(GatherSet g, con
     float* __restrict__ dst = g.dst[k] + (int64_t)m * g.ldd[k];
     for (int c = threadIdx.x; c < g.cols[k]; c += blockDim.x) dst[c] = r >= 0 ? src[c] : 0.f;
 }
-__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ out) {
-    __shared__ float sm[16];
-    float acc = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) acc += g[i] * g[i];
-    acc = block_sum(acc, sm);
-    if (threadIdx.x == 0) unsafeAtomicAdd(out, acc);
-}
-template <bool ZERO>       // ZERO: the gradient is left ZEROED (optimizer.zero_grad() fused into the sweep) instead of scaled and clipped
-__global__ __launch_bounds__(256) void clip_adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                        float* __restrict__ v, int64_t n, const float* __restrict__ sumsq,
-                                                        float max_norm, float lr, float b1, float b2, float eps, float wd, float bc1,
-                                                        float bc2, float gscale, uint16_t* __restrict__ p16) {
-    // misc/utils.py:193: coef = clip / max(total_norm, clip); gscale (1/world after a SUM all-reduce) is applied first
-    const float coef = gscale * (max_norm > 0.f ? max_norm / fmaxf(sqrtf(sumsq[0]) * gscale, max_norm) : 1.f);
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float gi = g[i] * coef;
-        g[i] = ZERO ? 0.f : gi;
-        if (wd != 0.f) gi += wd * p[i];
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi; v[i] = vi;
-        const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-        const float pn = p[i] - (lr / bc1) * (mi / denom);
-        p[i] = pn;
-        if (p16) p16[i] = (uint16_t)subgc_f2bf(pn);              // the bf16 weight snapshot the bf16 GEMMs read, refreshed in the same sweep
-    }
-}
-
-// float4 forms (n % 4 == 0, 16-byte aligned buffers: the flat parameter bucket always is): 1 KB per wave instruction
-__global__ __launch_bounds__(256) void sumsq_vec_kernel(const float4* __restrict__ g, int64_t n4, float* __restrict__ out) {
-    __shared__ float sm[16];
-    float acc = 0.f;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    for (; i + 3 * stride < n4; i += 4 * stride) {              // four loads in flight per thread: a quarter of the workgroups keeps the bytes in flight
-        const float4 x0 = g[i], x1 = g[i + stride], x2 = g[i + 2 * stride], x3 = g[i + 3 * stride];
-        acc += x0.x * x0.x + x0.y * x0.y + x0.z * x0.z + x0.w * x0.w;
-        acc += x1.x * x1.x + x1.y * x1.y + x1.z * x1.z + x1.w * x1.w;
-        acc += x2.x * x2.x + x2.y * x2.y + x2.z * x2.z + x2.w * x2.w;
-        acc += x3.x * x3.x + x3.y * x3.y + x3.z * x3.z + x3.w * x3.w;
-    }
-    for (; i < n4; i += stride) {
-        const float4 x = g[i];
-        acc += x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w;
-    }
-    acc = block_sum(acc, sm);
-    if (threadIdx.x == 0) unsafeAtomicAdd(out, acc);
-}
-template <bool ZERO>
-__global__ __launch_bounds__(256) void clip_adam_vec_kernel(float4* __restrict__ p, float4* __restrict__ g, float4* __restrict__ m,
-                                                            float4* __restrict__ v, int64_t n4, const float* __restrict__ sumsq,
-                                                            float max_norm, float lr, float b1, float b2, float eps, float wd, float bc1,
-                                                            float bc2, float gscale, uint16_t* __restrict__ p16) {
-    const float coef = gscale * (max_norm > 0.f ? max_norm / fmaxf(sqrtf(sumsq[0]) * gscale, max_norm) : 1.f);
-    const float rs2 = sqrtf(bc2), step = lr / bc1;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (int64_t)gridDim.x * blockDim.x) {
-        float4 P = p[i], G = g[i], M = m[i], V = v[i];
-        float* pp = &P.x; float* gg = &G.x; float* mm = &M.x; float* vv = &V.x;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {                                          // same arithmetic, element by element, as clip_adam_kernel
-            float gi = gg[e] * coef;
-            gg[e] = gi;
-            if (wd != 0.f) gi += wd * pp[e];
-            const float mi = b1 * mm[e] + (1.f - b1) * gi;
-            const float vi = b2 * vv[e] + (1.f - b2) * gi * gi;
-            mm[e] = mi; vv[e] = vi;
-            const float denom = sqrtf(vi) / rs2 + eps;
-            pp[e] = pp[e] - step * (mi / denom);
-        }
-        g[i] = ZERO ? make_float4(0.f, 0.f, 0.f, 0.f) : G; m[i] = M; v[i] = V; p[i] = P;
-        if (p16) *reinterpret_cast<uint2*>(p16 + 4 * i) = subgc_pack4(P.x, P.y, P.z, P.w);
-    }
-}
-
 inline int ew_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192)); }
 
 }  // namespace
@@ -1177,61 +1103,6 @@ SUBGC_API int subgc_gather_rows_multi_i64(int count, const float* s0, int64_t ld
     hipLaunchKernelGGL(gather_rows_multi_kernel<int64_t>, dim3(M, count), dim3(256), 0, (hipStream_t)stream, g, rows, M);
     return subgc::check_launch("subgc_gather_rows_multi_i64");
 }
-SUBGC_API int subgc_sumsq_f32(const float* g, int64_t n, float* sumsq, void* stream) {
-    SUBGC_REQUIRE(n >= 0, "sumsq: bad size");
-    SUBGC_REQUIRE(!subgc::deterministic(), "sumsq: adds with float atomics; in deterministic mode call subgc_sumsq_f32_ws");
-    if (n == 0) return SUBGC_OK;
-    SUBGC_REQUIRE(g && sumsq, "sumsq: null pointer");
-    if (n % 4 == 0 && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
-        // one same-address float atomic per workgroup: 2048 of them queue memory-side for ~20 us (a 13 MB slice took 35 us), 512 do not
-        hipLaunchKernelGGL(sumsq_vec_kernel, dim3(std::min(ew_grid(n / 4), 512)), dim3(256), 0, (hipStream_t)stream,
-                           reinterpret_cast<const float4*>(g), n / 4, sumsq);
-        return subgc::check_launch("subgc_sumsq_f32");
-    }
-    hipLaunchKernelGGL(sumsq_kernel, dim3(std::min(ew_grid(n), 1024)), dim3(256), 0, (hipStream_t)stream, g, n, sumsq);
-    return subgc::check_launch("subgc_sumsq_f32");
-}
-SUBGC_API int subgc_sumsq_f32_ws(const float* g, int64_t n, float* sumsq, void* workspace, size_t ws_bytes, void* stream) {
-    if (!subgc::deterministic()) return subgc_sumsq_f32(g, n, sumsq, stream);
-    SUBGC_REQUIRE(n >= 0, "sumsq_ws: bad size");
-    if (n == 0) return SUBGC_OK;
-    SUBGC_REQUIRE(g && sumsq, "sumsq_ws: null pointer");
-    return subgc::det_sumsq(g, n, sumsq, workspace, ws_bytes, (hipStream_t)stream);
-}
-namespace {
-template <bool ZERO>
-int clip_adam_launch(float* p, float* g, float* m, float* v, int64_t n, const float* sumsq, float max_norm, float lr, float beta1, float beta2, float eps,
-                     float weight_decay, int step, float grad_scale, uint16_t* p_bf16, void* stream) {
-    SUBGC_REQUIRE(n >= 0 && step >= 1 && grad_scale > 0.f, "clip_adam_step: bad arguments");
-    if (n == 0) return SUBGC_OK;
-    SUBGC_REQUIRE(p && g && m && v && sumsq, "clip_adam_step: null pointer");
-    const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
-    auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (n % 4 == 0 && al(p) && al(g) && al(m) && al(v) && (reinterpret_cast<uintptr_t>(p_bf16) & 7) == 0) {
-        hipLaunchKernelGGL(clip_adam_vec_kernel<ZERO>, dim3(ew_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<float4*>(p),
-                           reinterpret_cast<float4*>(g), reinterpret_cast<float4*>(m), reinterpret_cast<float4*>(v), n / 4, sumsq, max_norm, lr,
-                           beta1, beta2, eps, weight_decay, bc1, bc2, grad_scale, p_bf16);
-        return subgc::check_launch("subgc_clip_adam_step");
-    }
-    hipLaunchKernelGGL(clip_adam_kernel<ZERO>, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, sumsq, max_norm, lr, beta1,
-                       beta2, eps, weight_decay, bc1, bc2, grad_scale, p_bf16);
-    return subgc::check_launch("subgc_clip_adam_step");
-}
-}  // namespace
-
-SUBGC_API int subgc_clip_adam_step(float* p, float* g, float* m, float* v, int64_t n, const float* sumsq, float max_norm, float lr,
-                                   float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, uint16_t* p_bf16,
-                                   void* stream) {
-    return clip_adam_launch<false>(p, g, m, v, n, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step, grad_scale, p_bf16, stream);
-}
-// the same sweep with optimizer.zero_grad() (train.py: called once per iteration) folded in: g is left ZEROED instead of scaled and clipped,
-// so the next step needs no fill pass over the gradient buffer
-SUBGC_API int subgc_clip_adam_step_zero(float* p, float* g, float* m, float* v, int64_t n, const float* sumsq, float max_norm, float lr,
-                                        float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, uint16_t* p_bf16,
-                                        void* stream) {
-    return clip_adam_launch<true>(p, g, m, v, n, sumsq, max_norm, lr, beta1, beta2, eps, weight_decay, step, grad_scale, p_bf16, stream);
-}
-
 // ---------------------------------------------------------------------------------------------------
 // Packed decoder: dst[s, :] = sum over the time steps t at which sentence s is live of src[ot[t] + s, :]
 // (the gradient of the loop-invariant fc->gates term; replaces T accumulate-copies).  M_t = ot[t+1] - ot[t] is

@@ -1,13 +1,14 @@
-// Fused global-norm clip + optimizer update over one flat fp32 bucket, for every rule misc/utils.py:223-239 (build_optimizer)
-// can construct: Adam, AdamW, SGD (plain / momentum / Nesterov), RMSprop, Adagrad.  The structure is that of clip_adam_vec_kernel
-// (decoder.hip): the clip coefficient is read from the caller's sum(g^2) accumulator, grad_scale is applied first, a float4 sweep
-// with a scalar form for unaligned buckets, the bf16 weight snapshot written in the same pass, and a `_zero` form that leaves the
-// gradient zeroed (optimizer.zero_grad() folded in).  The update rule is a template parameter; each follows the single-tensor
-// code path of the torch class build_optimizer constructs, operation by operation.
+// The optimizer step over one flat fp32 bucket: the squared gradient norm (subgc_sumsq_f32) and the fused global-norm clip + update
+// sweep that consumes it (subgc_clip_optim_step), for every rule misc/utils.py:223-239 (build_optimizer) can construct: Adam, AdamW,
+// SGD (plain / momentum / Nesterov), RMSprop, Adagrad.  The sweep reads the clip coefficient from the caller's sum(g^2) accumulator,
+// applies grad_scale first, runs as a float4 sweep with a scalar form for unaligned buckets, writes the bf16 weight snapshot in the same
+// pass, and has a `_zero` form that leaves the gradient zeroed (optimizer.zero_grad() folded in).  The update rule is a template
+// parameter; each follows the single-tensor code path of the torch class build_optimizer constructs, operation by operation.
 //
 // Parameters torch would SKIP (their .grad is None: the reference's dead GCN units and unused class embeddings) are not touched:
 // the caller hands a device table of live [lo, hi) element ranges; every element outside them keeps its weight and its state
-// (the `_zero` form still zeroes its gradient).  Purely elementwise: no atomics, nothing for deterministic mode to do.
+// (the `_zero` form still zeroes its gradient).  Without a table (live = NULL: parallel.FlatAdam) every element is swept.  The sweep is
+// purely elementwise: no atomics, nothing for deterministic mode to do (the norm's fixed-order form is det_sumsq, det.hip).
 #include "common.h"
 #include "bf16_util.h"
 
@@ -15,6 +16,36 @@
 #include <cmath>
 
 namespace {
+
+inline int ew_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192)); }
+
+__global__ __launch_bounds__(256) void sumsq_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ out) {
+    __shared__ float sm[16];
+    float acc = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) acc += g[i] * g[i];
+    acc = block_sum(acc, sm);
+    if (threadIdx.x == 0) unsafeAtomicAdd(out, acc);
+}
+// float4 forms (n % 4 == 0, 16-byte aligned buffers: the flat parameter bucket always is): 1 KB per wave instruction
+__global__ __launch_bounds__(256) void sumsq_vec_kernel(const float4* __restrict__ g, int64_t n4, float* __restrict__ out) {
+    __shared__ float sm[16];
+    float acc = 0.f;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; i + 3 * stride < n4; i += 4 * stride) {              // four loads in flight per thread: a quarter of the workgroups keeps the bytes in flight
+        const float4 x0 = g[i], x1 = g[i + stride], x2 = g[i + 2 * stride], x3 = g[i + 3 * stride];
+        acc += x0.x * x0.x + x0.y * x0.y + x0.z * x0.z + x0.w * x0.w;
+        acc += x1.x * x1.x + x1.y * x1.y + x1.z * x1.z + x1.w * x1.w;
+        acc += x2.x * x2.x + x2.y * x2.y + x2.z * x2.z + x2.w * x2.w;
+        acc += x3.x * x3.x + x3.y * x3.y + x3.z * x3.z + x3.w * x3.w;
+    }
+    for (; i < n4; i += stride) {
+        const float4 x = g[i];
+        acc += x.x * x.x + x.y * x.y + x.z * x.z + x.w * x.w;
+    }
+    acc = block_sum(acc, sm);
+    if (threadIdx.x == 0) unsafeAtomicAdd(out, acc);
+}
 
 struct OptimHyper {
     float lr, a, b, eps, wd;
@@ -26,13 +57,13 @@ struct OptimHyper {
 // one element: p, its state s1 (exp_avg | momentum_buffer | square_avg | sum) and s2 (exp_avg_sq), gi = the scaled, clipped gradient
 template <int RULE>
 __device__ __forceinline__ void optim_elem(float& p, float gi, float& s1, float& s2, const OptimHyper& h) {
-    if constexpr (RULE == SUBGC_OPTIM_ADAM) {                 // the arithmetic of clip_adam_kernel (torch/optim/adam.py, L2 decay in the gradient)
-        if (h.wd != 0.f) gi += h.wd * p;
-        const float mi = h.a * s1 + (1.f - h.a) * gi;
-        const float vi = h.b * s2 + (1.f - h.b) * gi * gi;
+    if constexpr (RULE == SUBGC_OPTIM_ADAM) {                 // torch/optim/adam.py, L2 decay in the gradient.  Every multiply-add is fused
+        if (h.wd != 0.f) gi = fmaf(h.wd, p, gi);              // by hand: the bits then do not depend on which products the compiler would
+        const float mi = fmaf(1.f - h.a, gi, h.a * s1);       // contract in a given instantiation (scalar / float4, ZERO or not; a
+        const float vi = fmaf(gi, (1.f - h.b) * gi, h.b * s2); // near-cancelling g coef + wd p turns an ulp there into 4e-6 of p)
         s1 = mi; s2 = vi;
         const float denom = sqrtf(vi) / h.c2 + h.eps;
-        p = p - h.c1 * (mi / denom);
+        p = fmaf(-h.c1, mi / denom, p);
     } else if constexpr (RULE == SUBGC_OPTIM_ADAMW) {        // adam.py _single_tensor_adam, decoupled_weight_decay: p *= 1 - lr wd first
         if (h.wd != 0.f) p = p * h.decay;
         const float w1 = 1.f - h.a;                           // exp_avg.lerp_(grad, 1 - beta1) (ATen's two-sided lerp)
@@ -141,8 +172,6 @@ __global__ __launch_bounds__(256) void clip_optim_vec_kernel(float4* __restrict_
     }
 }
 
-inline int ew_grid(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192)); }
-
 template <int RULE, bool ZERO>
 int launch_rule(float* p, float* g, float* s1, float* s2, int64_t n, const int64_t* live, int nb, const float* sumsq, float max_norm,
                 float grad_scale, const OptimHyper& h, uint16_t* p16, hipStream_t stream) {
@@ -182,7 +211,7 @@ int clip_optim_launch(int rule, float* p, float* g, float* s1, float* s2, int64_
     OptimHyper h{};
     h.lr = lr; h.a = h0; h.b = h1; h.eps = eps; h.wd = weight_decay;
     h.nesterov = flags & 1; h.first = (flags >> 1) & 1;
-    if (adam) {                                   // bias corrections as clip_adam_launch computes them
+    if (adam) {                                   // bias corrections, in fp32
         const float bc1 = 1.f - powf(h0, (float)step), bc2 = 1.f - powf(h1, (float)step);
         h.c1 = lr / bc1; h.c2 = sqrtf(bc2);
         h.decay = (float)(1.0 - (double)lr * (double)weight_decay);
@@ -205,6 +234,28 @@ int clip_optim_launch(int rule, float* p, float* g, float* s1, float* s2, int64_
 }
 
 }  // namespace
+
+SUBGC_API int subgc_sumsq_f32(const float* g, int64_t n, float* sumsq, void* stream) {
+    SUBGC_REQUIRE(n >= 0, "sumsq: bad size");
+    SUBGC_REQUIRE(!subgc::deterministic(), "sumsq: adds with float atomics; in deterministic mode call subgc_sumsq_f32_ws");
+    if (n == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(g && sumsq, "sumsq: null pointer");
+    if (n % 4 == 0 && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+        // one same-address float atomic per workgroup: 2048 of them queue memory-side for ~20 us (a 13 MB slice took 35 us), 512 do not
+        hipLaunchKernelGGL(sumsq_vec_kernel, dim3(std::min(ew_grid(n / 4), 512)), dim3(256), 0, (hipStream_t)stream,
+                           reinterpret_cast<const float4*>(g), n / 4, sumsq);
+        return subgc::check_launch("subgc_sumsq_f32");
+    }
+    hipLaunchKernelGGL(sumsq_kernel, dim3(std::min(ew_grid(n), 1024)), dim3(256), 0, (hipStream_t)stream, g, n, sumsq);
+    return subgc::check_launch("subgc_sumsq_f32");
+}
+SUBGC_API int subgc_sumsq_f32_ws(const float* g, int64_t n, float* sumsq, void* workspace, size_t ws_bytes, void* stream) {
+    if (!subgc::deterministic()) return subgc_sumsq_f32(g, n, sumsq, stream);
+    SUBGC_REQUIRE(n >= 0, "sumsq_ws: bad size");
+    if (n == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(g && sumsq, "sumsq_ws: null pointer");
+    return subgc::det_sumsq(g, n, sumsq, workspace, ws_bytes, (hipStream_t)stream);
+}
 
 SUBGC_API int subgc_clip_optim_step(int rule, float* p, float* g, float* s1, float* s2, int64_t n, const int64_t* live, int n_live,
                                     const float* sumsq, float max_norm, float grad_scale, float lr, float h0, float h1, float eps,

@@ -103,16 +103,16 @@ class FusedOptimizer:
     """One torch.optim rule ('adam', 'adamw', 'sgd', 'rmsprop', 'adagrad'; hyperparameters as the torch class takes them) with the
     global-norm clip, over the model's flat buffers.  `fold_zero_grad`: the default of step(zero_grad=...), which leaves the gradient
     bucket zeroed by the sweep itself so that the next zero_grad() costs nothing (then the clipped gradients are not readable after the
-    step, as they are under torch)."""
+    step, as they are under torch).  `skip_dead=False` sweeps the whole bucket: no parameter is skipped (parallel.FlatAdam)."""
 
-    def __init__(self, model, kind, clip_norm=10.0, fold_zero_grad=False, **hyper):
+    def __init__(self, model, kind, clip_norm=10.0, fold_zero_grad=False, skip_dead=True, **hyper):
         if kind not in _CLASSES:
             raise ValueError(f"unknown optimizer {kind!r} (one of {sorted(_CLASSES)})")
         probe = _CLASSES[kind]([torch.zeros(1, requires_grad=True)], **hyper)       # torch validates and fills in its defaults
         self.model, self.kind, self.clip_norm, self.fold_zero_grad = model, kind, clip_norm, fold_zero_grad
         self.defaults = dict(probe.defaults)
         self.names = reference_param_names(model)
-        self.skipped = frozenset(skipped_param_names(model))
+        self.skipped = frozenset(skipped_param_names(model) if skip_dead else ())
         self.param_groups = [dict({k: v for k, v in probe.param_groups[0].items() if k != "params"}, params=[model.P(n) for n in self.names])]
         self._rule(self.param_groups[0])
         fp = model.flat_params

@@ -28,6 +28,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from .optim import FusedOptimizer
+
 
 def init_distributed(backend=None):
     """Join the process group described by RANK / WORLD_SIZE / MASTER_* (torchrun env)."""
@@ -127,7 +129,7 @@ class GradBucketReducer:
         the stream ordering between the backward kernels and the all-reduce; the sum over one rank is the identity).
         `timing`: bracket the step with HIP events on the compute stream (`report()`): when each slice's collective could start,
         and how long the compute stream then WAITED for the collectives after the backward's last kernel = the exposed communication.
-        `optimizer` (a FlatAdam): with several ranks the squared gradient norm its global-norm clip needs is accumulated BUCKET BY BUCKET
+        `optimizer` (any FusedOptimizer): with several ranks the squared gradient norm its global-norm clip needs is accumulated BUCKET BY BUCKET
         as each slice becomes final -- behind the slice's all-reduce, on a side
         stream, so neither the backward nor the later collectives wait for it -- instead of one pass over the whole 280 MB buffer after
         the last collective.  (One rank has nothing to hide it behind: the whole-buffer pass in `FlatAdam.step` stays.)  What cannot move is the clip + Adam sweep itself: the clip coefficient is a function of the norm of ALL
@@ -285,60 +287,24 @@ class GradBucketReducer:
         self._handles = []
 
 
-class FlatAdam:
+class FlatAdam(FusedOptimizer):
     """Global-norm clip + Adam over the flat bucket in one fused sweep
-    (reference misc/utils.py:174-200 `clip_gradient_norm(optimizer, 10.)` + `torch.optim.Adam`).
+    (reference misc/utils.py:174-200 `clip_gradient_norm(optimizer, 10.)` + `torch.optim.Adam`): the "adam" rule of
+    `optim.FusedOptimizer` over the WHOLE bucket, state in `m` / `v`.  Like every FusedOptimizer, `step` refuses gradients that
+    are not views of the flat bucket (call `model.flatten_grads()` / `GradBucketReducer.prepare()` before the forward).
 
     One difference from `torch.optim.Adam`, visible only with `weight_decay > 0` (the reference trains with 0, opts.py): torch
     skips a parameter whose `.grad` is None, the flat sweep has no such notion -- a parameter the step never touched (e.g. the
     unused `ctx2att` of a Sub-GC model) has a zero gradient slot and still receives its decay term."""
 
     def __init__(self, model, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, clip_norm=10.0):
-        self.model, self.lr, self.betas, self.eps, self.wd, self.clip = model, lr, betas, eps, weight_decay, clip_norm
-        self.m = torch.zeros_like(model.flat_params)
-        self.v = torch.zeros_like(model.flat_params)
-        self.sumsq = torch.zeros(1, device=model.flat_params.device)
-        self.t = 0
-        self.reducer = None            # a GradBucketReducer(optimizer=self) accumulates the clip norm slice by slice (begin_step / accumulate)
-        self._have = None              # stages whose squared norm is already in self.sumsq for the gradients of the current step
+        super().__init__(model, "adam", clip_norm=clip_norm, skip_dead=False, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
 
-    def begin_step(self):
-        """(reducer.prepare) a new set of gradients: the norm accumulator starts from zero."""
-        from . import ops
-        ops.fill_(self.sumsq, 0.0)
-        self._have = set()
-
-    def accumulate(self, stage, lo, hi):
-        """sumsq += |flat_grads[lo:hi]|^2 on the CURRENT stream (the slice is final -- and, with several ranks, reduced -- there)."""
-        from . import ops
-        if self._have is None or stage in self._have:
-            return
-        self._have.add(stage)
-        ops.sumsq(self.model.flat_grads[lo:hi], self.sumsq)
+    m = property(lambda self: self._s1)
+    v = property(lambda self: self._s2)
 
     def step(self, grad_scale=1.0, zero_grad=False):
         """`zero_grad`: leave the gradient buffer ZEROED by the sweep itself (= this step followed by the `optimizer.zero_grad()` every
         training iteration starts with, train.py) -- the next `flatten_grads` / `GradBucketReducer.prepare` then skips its fill pass over
         the buffer.  Default: torch's semantics, the (scaled, clipped) gradients stay readable after the step."""
-        from . import ops
-        self.t += 1
-        if self._have:                                          # some slices are in already: add whatever was not announced early (always the fusion slice)
-            for st, lo, hi in self.reducer.buckets:
-                if hi > lo:
-                    self.accumulate(st, lo, hi)
-            self._have = None
-        else:                                                   # nothing accumulated (one rank, or no reducer): one pass over the whole buffer
-            self._have = None
-            ops.fill_(self.sumsq, 0.0)
-            ops.sumsq(self.model.flat_grads, self.sumsq)
-        m = self.model
-        snap = m.weights_b16() if getattr(m, "bf16_storage", False) else None     # compute_dtype = bf16: refreshed in the same sweep
-        ops.clip_adam_step(m.flat_params, m.flat_grads, self.m, self.v, self.sumsq, self.clip, self.lr,
-                           self.betas[0], self.betas[1], self.eps, self.wd, self.t, grad_scale, p_bf16=snap, zero_grad=zero_grad)
-        from . import ops as _ops
-        m.__dict__["_grads_are_zero"] = (m.flat_grads.data_ptr(), m.flat_grads._version, _ops.GRAD_WRITES[0]) if zero_grad else None
-        # the kernel wrote the weights through raw pointers: no torch version counter moved, so the decode-time snapshots
-        # (x->gates table, K-concatenated LSTM matrices, captured hipGraphs) must be told explicitly
-        m.invalidate_decode_caches()
-        if snap is not None:
-            m.weights_b16(fresh_from_optimizer=True)                               # ... while the bf16 weight snapshot is already current
+        super().step(grad_scale=grad_scale, zero_grad=zero_grad)

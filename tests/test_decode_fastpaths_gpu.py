@@ -235,7 +235,7 @@ def test_clip_adam_grad_scale_equals_scaling_first(n):
         if not folded:
             gr.mul_(0.25)
         ops.sumsq(gr, ss)
-        ops.clip_adam_step(p, gr, m, v, ss, 10.0, 5e-4, 0.9, 0.999, 1e-8, 0.01, 3, 0.25 if folded else 1.0)
+        ops.clip_optim_step("adam", p, gr, m, v, None, ss, 10.0, 0.25 if folded else 1.0, 5e-4, 0.9, 0.999, 1e-8, 0.01, 3)
         outs.append((p, gr, m, v))
     for a, b in zip(*outs):
         torch.testing.assert_close(a, b, atol=1e-6, rtol=1e-5)

@@ -456,18 +456,18 @@ def test_clip_adam_matches_torch():
     p, g = p0.clone(), g0.clone(); m = torch.zeros(n, device=DEV); v = torch.zeros(n, device=DEV)
     ss = torch.zeros(1, device=DEV)
     ops.sumsq(g, ss)
-    ops.clip_adam_step(p, g, m, v, ss, 10.0, 5e-4, 0.9, 0.999, 1e-8, 0.0, 1)
+    ops.clip_optim_step("adam", p, g, m, v, None, ss, 10.0, 1.0, 5e-4, 0.9, 0.999, 1e-8, 0.0, 1)
     close(g, pr.grad, atol=1e-6); close(p, pr.detach(), atol=1e-6)
-    # the same sweep with the iteration's optimizer.zero_grad() folded in (subgc_clip_adam_step_zero): identical update, gradient zeroed
+    # the same sweep with the iteration's optimizer.zero_grad() folded in (subgc_clip_optim_step_zero): identical update, gradient zeroed
     for n2 in (n, 10008):                                     # scalar and float4 forms
         p2 = torch.cat([p0, p0[:n2 - n]]) if n2 > n else p0.clone()
         g2 = torch.cat([g0, g0[:n2 - n]]) if n2 > n else g0.clone()
         pa, ga = p2.clone(), g2.clone()
         ma, va, mb, vb = (torch.zeros(n2, device=DEV) for _ in range(4))
         s2 = torch.zeros(1, device=DEV); ops.sumsq(g2, s2)
-        ops.clip_adam_step(pa, ga, ma, va, s2, 10.0, 5e-4, 0.9, 0.999, 1e-8, 0.0, 1)
+        ops.clip_optim_step("adam", pa, ga, ma, va, None, s2, 10.0, 1.0, 5e-4, 0.9, 0.999, 1e-8, 0.0, 1)
         pb, gb = p2.clone(), g2.clone()
-        ops.clip_adam_step(pb, gb, mb, vb, s2, 10.0, 5e-4, 0.9, 0.999, 1e-8, 0.0, 1, zero_grad=True)
+        ops.clip_optim_step("adam", pb, gb, mb, vb, None, s2, 10.0, 1.0, 5e-4, 0.9, 0.999, 1e-8, 0.0, 1, zero_grad=True)
         assert torch.equal(pa, pb) and torch.equal(ma, mb) and torch.equal(va, vb) and float(gb.abs().max()) == 0.0 and float(ga.abs().max()) > 0
 
 

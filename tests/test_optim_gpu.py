@@ -184,27 +184,36 @@ def test_sweep_matches_torch_single_tensor_with_skipped_ranges(kind, n, zero):
             close(s1[lo:hi], st[i][key], f"{kind} state {key}", atol=1e-6, rtol=1e-5)
 
 
-def test_adam_rule_equals_the_existing_adam_sweep():
-    """SUBGC_OPTIM_ADAM is the arithmetic of subgc_clip_adam_step (the compiler may contract the two kernels' products into fused
-    multiply-adds differently: equal to the last bits), and the snapshot is the bf16 cast of the updated weights."""
+def _whole_bucket_against_full_table(n, zero, wd):
     gen = torch.Generator().manual_seed(3)
-    n = 1 << 16
     p = torch.randn(n, generator=gen).to(DEV)
     a = [p.clone(), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)]
     b = [p.clone(), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV)]
     sa, sb = torch.empty(n, device=DEV, dtype=torch.bfloat16), torch.empty(n, device=DEV, dtype=torch.bfloat16)
     ss = torch.zeros(1, device=DEV)
+    table = torch.tensor([0, n], dtype=torch.int64, device=DEV)
     for t in range(1, 4):
         g = (torch.randn(n, generator=gen) * 0.1).to(DEV)
         ops.fill_(ss, 0.0)
         ops.sumsq(g, ss)
         ga, gb = g.clone(), g.clone()
-        ops.clip_adam_step(a[0], ga, a[1], a[2], ss, 10.0, 1e-3, 0.9, 0.999, 1e-8, 0.01, t, p_bf16=sa)
-        ops.clip_optim_step("adam", b[0], gb, b[1], b[2], None, ss, 10.0, 1.0, 1e-3, 0.9, 0.999, 1e-8, 0.01, t, p_bf16=sb)
-    assert torch.equal(ga, gb)
-    for x, y in zip(a, b):
-        torch.testing.assert_close(x, y, atol=1e-7, rtol=2e-6)
+        ops.clip_optim_step("adam", a[0], ga, a[1], a[2], None, ss, 10.0, 1.0, 1e-3, 0.9, 0.999, 1e-8, wd, t, p_bf16=sa, zero_grad=zero)
+        ops.clip_optim_step("adam", b[0], gb, b[1], b[2], table, ss, 10.0, 1.0, 1e-3, 0.9, 0.999, 1e-8, wd, t, p_bf16=sb, zero_grad=zero)
+        assert torch.equal(ga, gb) and (float(ga.abs().max()) == 0.0) == zero
+    for x, y in zip(a + [sa], b + [sb]):
+        assert torch.equal(x, y), (n, zero, wd)
+    assert not torch.equal(a[0], p) and float(a[1].abs().max()) > 0 and float(a[2].abs().max()) > 0
     assert torch.equal(sb, b[0].to(torch.bfloat16)) and torch.equal(sa, a[0].to(torch.bfloat16))
+
+
+def test_adam_whole_bucket_equals_a_live_table_covering_it():
+    """The Adam rule with no live table (what parallel.FlatAdam launches) against the same rule with the one live range [0, n): the
+    same arithmetic in the same kernel, so every buffer is bit-identical after three steps; and the snapshot is the bf16 cast of the
+    updated weights.  The float4 form and the scalar form (n = 65539), both ZERO forms, weight_decay 0 and 0.01."""
+    for n in (1 << 16, (1 << 16) + 3):
+        for zero in (False, True):
+            for wd in (0.0, 0.01):
+                _whole_bucket_against_full_table(n, zero, wd)
 
 
 # ------------------------------------------------------------------------------------------------ against torch on the golden model

@@ -208,7 +208,9 @@ def _adam_worker(rank, world, port, q):
         calls.append(("sumsq", g.data_ptr(), g.numel()))
         out += (g.double() ** 2).sum().float(); return out
 
-    def clip_adam_step(p, g, m, v, ss, max_norm, lr, b1, b2, eps, wd, step, grad_scale=1.0, p_bf16=None, zero_grad=False):
+    def clip_optim_step(rule, p, g, m, v, live, ss, max_norm, grad_scale, lr, b1, b2, eps, wd, step, nesterov=False, first=False,
+                        p_bf16=None, zero_grad=False):
+        assert rule == "adam" and live is None and wd == 0
         calls.append(("sweep", float(ss)))
         coef = grad_scale * (max_norm / max(float(ss.sqrt()) * grad_scale, max_norm))
         gi = g * coef
@@ -216,7 +218,7 @@ def _adam_worker(rank, world, port, q):
         p.sub_(lr / (1 - b1 ** step) * m / ((v / (1 - b2 ** step)).sqrt() + eps))
         g.zero_() if zero_grad else g.copy_(gi)
 
-    ops.fill_, ops.sumsq, ops.clip_adam_step = fill_, sumsq, clip_adam_step
+    ops.fill_, ops.sumsq, ops.clip_optim_step = fill_, sumsq, clip_optim_step
     parallel.init_distributed("gloo")
     model = models.setup(Golden("subgc_train").opt(caption_model="topdown"))
     model.invalidate_decode_caches = lambda: None

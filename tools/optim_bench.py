@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """Stand-alone timing of the fused clip + optimizer sweep (subgc_clip_optim_step) for every rule of subgc.optim.build_optimizer on a
-BASELINE config's flat bucket (default Full_GC_Kar: 76.1 M parameters, bf16 weight snapshot written in the sweep), beside the existing
-clip + Adam sweep (subgc_clip_adam_step, what FlatAdam launches).  Interleaved rounds: every round times each sweep back to back.
+BASELINE config's flat bucket (default Full_GC_Kar: 76.1 M parameters, bf16 weight snapshot written in the sweep), beside the Adam rule
+over the whole bucket (no live table: what parallel.FlatAdam launches).  Interleaved rounds: every round times each sweep back to back.
 
     python tools/optim_bench.py [--config full_gc_kar] [--rounds 5] [--iters 20]
 
 Bytes per live parameter (fp32 masters, states and gradient, + 2 B of bf16 snapshot when the config has one): Adam / AdamW read
 p, g, m, v and write them back (32 B); SGD with momentum, RMSprop and Adagrad keep one state (24 B).  Parameters torch skips move
-nothing (the old Adam sweep updates them too, so its count is the whole bucket).  Prints a table and a final JSON line with the median
+nothing (FlatAdam's sweep updates them too, so its count is the whole bucket).  Prints a table and a final JSON line with the median
 time of each sweep and its rate (not the achievable-HBM share: the MI355X sustains about 6.3 of its 8 TB/s)."""
 import argparse
 import json
@@ -49,8 +49,8 @@ def main():
 
     sweeps = {}
     mo, vo = torch.zeros_like(m.flat_params), torch.zeros_like(m.flat_params)
-    sweeps["adam (clip_adam_step)"] = (lambda: ops.clip_adam_step(m.flat_params, g, mo, vo, sumsq, 10.0, 0.0, 0.9, 0.999, 1e-8, 0.0, 5,
-                                                                   p_bf16=snap), n * (32 + b16))
+    sweeps["adam, whole bucket (FlatAdam)"] = (lambda: ops.clip_optim_step("adam", m.flat_params, g, mo, vo, None, sumsq, 10.0, 1.0, 0.0, 0.9,
+                                                                           0.999, 1e-8, 0.0, 5, p_bf16=snap), n * (32 + b16))
     for rule in RULES:
         o.optim = rule
         fo = optim.build_optimizer(m, o)
@@ -82,11 +82,12 @@ def main():
     rows = {}
     print(f"{args.config}: {n / 1e6:.1f} M parameters in the bucket, bf16 snapshot {'on' if snap is not None else 'off'}; "
           f"{args.rounds} rounds x {args.iters} sweeps")
-    print(f"{'sweep':24s} {'MB moved':>9s} {'median us':>10s} {'min us':>8s} {'TB/s':>6s}")
+    print(f"{'sweep':30s} {'MB moved':>9s} {'median us':>10s} {'min us':>8s} {'max us':>8s} {'TB/s':>6s}")
     for k, (_, nbytes) in sweeps.items():
-        med, lo = statistics.median(times[k]), min(times[k])
-        rows[k] = dict(bytes=nbytes, median_us=round(med * 1e3, 1), min_us=round(lo * 1e3, 1), tb_s=round(nbytes / (med * 1e-3) / 1e12, 2))
-        print(f"{k:24s} {nbytes / 1e6:9.1f} {med * 1e3:10.1f} {lo * 1e3:8.1f} {rows[k]['tb_s']:6.2f}")
+        med, lo, hi = statistics.median(times[k]), min(times[k]), max(times[k])
+        rows[k] = dict(bytes=nbytes, median_us=round(med * 1e3, 1), min_us=round(lo * 1e3, 1), max_us=round(hi * 1e3, 1),
+                       tb_s=round(nbytes / (med * 1e-3) / 1e12, 2))
+        print(f"{k:30s} {nbytes / 1e6:9.1f} {med * 1e3:10.1f} {lo * 1e3:8.1f} {hi * 1e3:8.1f} {rows[k]['tb_s']:6.2f}")
     print(json.dumps(dict(config=args.config, params=n, bf16_snapshot=snap is not None, rounds=args.rounds, iters=args.iters, sweeps=rows)))
 
 
