@@ -656,6 +656,25 @@ int subgc_decode_pick(const float* logp, int64_t ld, int n, int V, int k, float 
                       int t, int64_t* seq, float* seqlp, int T, int64_t* next_tok, int32_t* unfinished,
                       int32_t* n_unfinished, const int32_t* prev_count, int raw_logits, void* stream);
 
+/* Sampling token choice for ANY k, with an optional nucleus cut (AttModel.py:295-303 `torch.topk(logprobs, self.the_k)` takes any
+ * the_k up to the row width; subgc_decode_pick stops at 8).  1 <= k <= V, V <= 16384, 0 < top_p <= 1 (1: off), temp > 0.
+ *   v      = log_softmax(logits / temp) over the row.
+ *   order  : float32 logit descending, ties to the smaller column -- ordered on the logit ITSELF (x -> x/temp - lse is monotone, so
+ *            this is a valid top-k order; a stable descending sort of the same float32 row reproduces it exactly).
+ *   kept   : the first k in that order; with top_p < 1 the shortest prefix of length m <= k whose summed exp(v_j) -- mass under the
+ *            FULL tempered distribution -- reaches top_p; at least one token; m = k when the k leading never reach top_p.
+ *   draw   : renormalise over the kept prefix, inverse CDF in that order with u[s] (NULL: 0): pick = #{j : u >= cdf_j}, clamped to
+ *            m - 1.  cdf_j is a fixed-order float32 sum: the same inputs give the same bits on every launch.
+ *   lp     = v[token], NOT renormalised (the reference gathers from the scattered tempered row, AttModel.py:299-303).
+ * Everything else is the contract of subgc_decode_pick: unfinished &= it > 0; it *= unfinished; seq[s, t] = it; seqlp[s, t] = lp
+ * (un-masked); next_tok[s] = it; *n_unfinished becomes non-zero iff some row is unfinished; prev_count == 0 writes nothing.
+ * raw_logits is accepted for symmetry: the tempered log-softmax is shift-invariant, so raw and normalised rows give the same result.
+ * Capturable (no synchronisation, no allocation); dynamic LDS = 8 bytes x the power of two >= k.  A nucleus or whole-row call whose
+ * last level exceeds 2048 entries is two launches (the second, with the large LDS, only works on rows the first left undecided). */
+int subgc_decode_sample(const float* logits, int64_t ld, int n, int V, int k, float top_p, float temp, const float* u,
+                        int t, int64_t* seq, float* seqlp, int T, int64_t* next_tok, int32_t* unfinished,
+                        int32_t* n_unfinished, const int32_t* prev_count, int raw_logits, void* stream);
+
 /* Beam search (CaptionModel.py:60 `torch.sort(logprobsf, 1, True)`, of which beam_step :62-72 reads only the
  * leading `beam` columns): vals[r, :k], idx[r, :k] = the k largest entries of row r of x[rows, cols] in
  * (value descending, index ascending) order.  log_softmax != 0: x holds raw logits and vals are

@@ -95,6 +95,14 @@ class AttModel(CaptionModel):
         self.topk_sampling = g("use_topk_sampling", 0) != 0
         self.topk_temp = g("topk_temp", 0.6)
         self.the_k = g("the_k", 3)
+        self.the_p = float(g("the_p", 1.0))                   # nucleus cut inside the top-k (1: off).  Not a reference option.
+        if self.topk_sampling:
+            # the reference fails at its first torch.topk (AttModel.py:297) for a k outside the logit row; here: at construction
+            if int(self.the_k) != self.the_k or not 1 <= self.the_k <= self.vocab_size + 1:
+                raise ValueError(f"the_k = {self.the_k}: top-k sampling needs 1 <= the_k <= vocab_size + 1 = {self.vocab_size + 1}")
+            if not 0.0 < self.the_p <= 1.0:
+                raise ValueError(f"the_p = {self.the_p}: the nucleus mass must lie in (0, 1] (1 = off)")
+            self.the_k = int(self.the_k)
         self.sct = g("sct", 0) != 0
         self.gpn_nms_thres = g("gpn_nms_thres", 0.75)
         self.gpn_max_subg = g("gpn_max_subg", 1)

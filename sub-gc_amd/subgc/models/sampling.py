@@ -214,14 +214,15 @@ class _GraphedLoop:
     The reference-shaped call decodes <= 10 rows per step: ~12 kernels of 5-30 us each, 21 steps -- launch-bound.  For a
     given row count the launch sequence is static (the early break is device-side), so it is captured once on buffers
     of fixed address and replayed per image; the image's prepared features are written into those buffers first.
-    Keyed by (rows, N, attention rows capacity, k, return_att) and by the version of the flat parameter buffer (the
+    Keyed by (rows, N, attention rows capacity, k, the_p, return_att) and by the version of the flat parameter buffer (the
     K-concatenated LSTM weights inside DecodeState are snapshots of the parameters).  Every launch inside the graph and around the
     replay is a C-ABI kernel: the small state tensors live in one arena (one zero fill, one snapshot copy per image)."""
 
-    def __init__(self, m, n, N, k, return_att, P, fb=None):
+    def __init__(self, m, n, N, k, return_att, P, fb=None, top_p=1.0):
         dev = m.flat_params.device
         T, R, A, L = m.seq_length, m.rnn_size, m.att_hid_size, m.GCN_dim
         self.n, self.N, self.T, self.k, self.return_att = n, N, T, k, return_att
+        self.top_p = top_p
         self.m, self.P, self.fb = m, P, fb                                        # fb: the graph starts from the selection's static buffers
         cap = n * N
         z = lambda *s, dt=torch.float32: ops.zero_(torch.empty(*s, device=dev, dtype=dt))
@@ -263,7 +264,7 @@ class _GraphedLoop:
             if t == T:
                 break
             ops.decode_pick(logp, self.k, self.topk_temp, None if self.u is None else self.u[t], t, self.seq, self.seqlp, self.it,
-                            self.unfinished, self.counts[t:t + 1], self.counts[t - 1:t] if t > 0 else None, raw=True)
+                            self.unfinished, self.counts[t:t + 1], self.counts[t - 1:t] if t > 0 else None, raw=True, top_p=self.top_p)
 
     def run(self, pr, uniforms, step_major=False):
         """-> (seq, seqlp, counts, AL, score_out, keep_out): the results are one snapshot copy of the arena's result block.
@@ -341,14 +342,15 @@ def _graphed_beam(m, n, N, P, opt, fb=None):
 
 
 def _graphed_loop(m, n, N, k, return_att, P, fb=None):
-    key = (n, N, k, return_att, None if fb is None else fb.G) + m.weights_version()
+    top_p = m.the_p if k else 1.0
+    key = (n, N, (k, top_p), return_att, None if fb is None else fb.G) + m.weights_version()
     cache = m.__dict__.setdefault("_graph_cache", {})
     if key not in cache:
         for old in [q for q in cache if q[:5] == key[:5]]:                       # parameters changed: drop the stale snapshot
             del cache[old]
         if len(cache) >= 64:                                                      # states share their weight snapshots: a graph is a few MB
             cache.clear()
-        cache[key] = _GraphedLoop(m, n, N, k, return_att, P, fb)
+        cache[key] = _GraphedLoop(m, n, N, k, return_att, P, fb, top_p)
     return cache[key]
 
 
@@ -528,7 +530,7 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
                 _forced_pick(logp, forced[:, t].contiguous(), k, m.topk_temp, t, seq, seqlp, it, unfinished, counts)
             else:
                 ops.decode_pick(logp, k, m.topk_temp, None if ut is None else ut[t], t, seq, seqlp, it,
-                                unfinished, counts[t:t + 1], counts[t - 1:t] if t > 0 else None, raw=True)
+                                unfinished, counts[t:t + 1], counts[t - 1:t] if t > 0 else None, raw=True, top_p=m.the_p if k else 1.0)
     if tap is not None and graphed is None:
         tap.update({"step_" + key_: torch.stack(v_, 0) for key_, v_ in steps_tap.items()})
         if not return_att:

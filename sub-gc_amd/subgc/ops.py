@@ -1408,10 +1408,22 @@ def step_active(labels, T):
     return active
 
 
-def decode_pick(logp, k, temp, u, t, seq, seqlp, next_tok, unfinished, n_unf, prev_count=None, raw=False):
+def decode_pick(logp, k, temp, u, t, seq, seqlp, next_tok, unfinished, n_unf, prev_count=None, raw=False, top_p=1.0):
+    """Greedy (k == 0) / top-k token choice.  k <= 8 without a nucleus cut runs subgc_decode_pick; a larger k or top_p < 1 runs the
+    radix-select kernel subgc_decode_sample."""
     n, V = logp.shape
+    if k > 8 or top_p != 1.0:
+        return decode_sample(logp, k, top_p, temp, u, t, seq, seqlp, next_tok, unfinished, n_unf, prev_count, raw)
     call("subgc_decode_pick", _ptr(logp), ld(logp), n, V, int(k), float(temp), _ptr(u), int(t), _ptr(seq, torch.int64), _ptr(seqlp),
          seq.size(1), _ptr(next_tok, torch.int64), _ptr(unfinished, torch.int32), _ptr(n_unf, torch.int32), _ptr(prev_count, torch.int32), int(raw), _stream())
+
+
+def decode_sample(logits, k, top_p, temp, u, t, seq, seqlp, next_tok, unfinished, n_unf, prev_count=None, raw=False):
+    """Top-k / nucleus token choice for any 1 <= k <= V (subgc_decode_sample; see include/subgc_hip.h for the order and cut rules)."""
+    n, V = logits.shape
+    call("subgc_decode_sample", _ptr(logits), ld(logits), n, V, int(k), float(top_p), float(temp), _ptr(u), int(t), _ptr(seq, torch.int64),
+         _ptr(seqlp), seq.size(1), _ptr(next_tok, torch.int64), _ptr(unfinished, torch.int32), _ptr(n_unf, torch.int32),
+         _ptr(prev_count, torch.int32), int(raw), _stream())
 
 
 def row_topk(x, k, vals, idx, log_softmax=True):
