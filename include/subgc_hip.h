@@ -3,7 +3,7 @@
  *
  * The reference (YiwuZhong/Sub-GC) has no FFI layer: its hot path is ATen calls made from
  * models/AttModel.py, models/lib/{gcn_backbone,graph_conv,graph_conv_unit,gpn}.py and
- * misc/utils.py.  Each of the 128 entry points below replaces the op site cited next to it (file:line in
+ * misc/utils.py.  Each of the 130 entry points below replaces the op site cited next to it (file:line in
  * /root/reference).  INTEGRATION.md shows the ctypes binding a maintainer adds.
  *
  * Contract for EVERY function:
@@ -725,6 +725,43 @@ int subgc_eval_rank_rows(const float* score, const int64_t* keep, const int64_t*
 int subgc_grounding_argmax(const float* AL, int64_t ld_t, int64_t ld_row, int N, int T1, const int64_t* seq, int T,
                            const int64_t* idx, int64_t ld_idx, const int32_t* seg, const int32_t* order, const int32_t* pick,
                            int I, int32_t* att2, int32_t* node, int32_t* n_words, void* stream);
+
+/* Consensus re-ranking, method 'cider' (misc/consensus_reranking/concensus_reranking_utils/consensus_reranking.py:152-174; the pair score
+ * is CiderScorer.compute_cider_sen_pair, misc/consensus_reranking/external/coco_caption_patch_mRNN_cr/cider_scorer_compute_sentence.py:187-264).
+ * Words are 16-bit ids (1 .. 65535, 0 never inside a sentence); an n-gram of order 1 .. 4 is one uint64 key, word j of it in bits
+ * 63-16j .. 48-16j, missing words zero.  All arithmetic fp64, summation orders fixed by the inputs: equal inputs give equal bits.  None
+ * of the three needs scratch.
+ *
+ * subgc_consensus_cook (precook + counts2vec, :15-30, :188-212): S sentences -> per sentence its DISTINCT n-grams in ascending key
+ * order with weight tf * (ref_len - log df), the four norms sqrt(sum of squared weights of an order) and the length = its number of
+ * BIGRAMS, max(words - 1, 0) (:209-210).  log df comes from ukeys [U] (sorted, distinct) / ulogdf [U] by binary search, absent = 0.
+ *   CSR mode (woff != NULL, int32 [S + 1]): sentence s = tok[woff[s] .. woff[s+1]), every id non-zero, at most max_words <= 256 words.
+ *   Row mode (woff NULL): sentence s = row s of tok [S, T], T <= 64: the ids before the first id <= 0, at most row_len[s] of them
+ *   (row_len NULL or a negative entry: no limit); with bad != NULL (uint8 [bad_n]) trailing words w with bad[w] != 0 are dropped unless
+ *   every word is one (decode_sequence's REMOVE_BAD_ENDINGS rule, misc/utils.py:74-80).
+ *   tok: int32, or int64 with tok64 != 0.  Sentence s writes keys / wts [4 * w0 .. 4 * w0 + cnt[s]) with w0 its first word's index in
+ *   tok (woff[s], or s * T), so keys / wts hold 4 x (words of tok) entries; cnt, blen int32 [S]; norm fp64 [S, 4].
+ * subgc_consensus_score (:155-169): image i owns candidate rows seg[i] .. seg[i+1]-1 (cooked in row mode with this T), of which the first
+ * top_k count (top_k = 0: all; at most max_cand).  Its neighbour captions are those of corpus images nn[i, 0 .. k) (int32 [I, nn_ld],
+ * k <= nn_ld, k <= 256) in that order, image j owning corpus sentences cap_off[j] .. cap_off[j+1]-1 (int32 [n_img + 1], n_caps in all;
+ * the corpus cooked in CSR mode over nwoff): at most max_caps <= 2048 of them per image -- the caller states the largest count, what
+ * lies beyond it is not scored.  Pair score = 10 x mean over the four orders of sum_g min(w_hyp[g], w_ref[g]) w_ref[g], divided by
+ * norm_hyp norm_ref where both are non-zero, times gauss[|length difference|] (fp64 [n_gauss], e^(-d^2 / (2 sigma^2)) from the host).
+ * sim[row] = the sum of the row's m largest pair scores (all, when fewer), added in descending order.  pair_out (may be NULL; fp64,
+ * row stride pair_ld >= max_caps): every pair score, column = position in the image's neighbour caption list.  Neighbour indices outside
+ * [0, n_img) are clamped; debug bounds mode reports them (and cap_off entries outside [0, n_caps]) instead.
+ * subgc_consensus_rank (:172): order[seg[i] + r] = image-local index of the r-th largest sim among the image's first top_k rows; EQUAL
+ * sums keep ascending candidate index (np.argsort(-sim) leaves ties open); first[i] (may be NULL) = order[seg[i]], 0 for an image with
+ * no rows: the `pick` of subgc_grounding_argmax, so consensus grounding needs no second pass (misc/grd_utils.py:31-35).          */
+int subgc_consensus_cook(const void* tok, int tok64, const int32_t* woff, int T, const int32_t* row_len, const uint8_t* bad, int bad_n,
+                         int S, int max_words, const uint64_t* ukeys, const double* ulogdf, int64_t U, double ref_len, uint64_t* keys,
+                         double* wts, int32_t* cnt, int32_t* blen, double* norm, void* stream);
+int subgc_consensus_score(const uint64_t* ckeys, const double* cw, const int32_t* ccnt, const int32_t* clen, const double* cnorm, int T,
+                          const int32_t* seg, int I, int max_cand, int top_k, const int32_t* nn, int nn_ld, int k,
+                          const int32_t* cap_off, int n_img, int n_caps, const int32_t* nwoff, const uint64_t* nkeys, const double* nw,
+                          const int32_t* ncnt, const int32_t* nlen, const double* nnorm, const double* gauss, int n_gauss, int m,
+                          int max_caps, double* sim, double* pair_out, int64_t pair_ld, void* stream);
+int subgc_consensus_rank(const double* sim, const int32_t* seg, int I, int top_k, int32_t* order, int32_t* first, void* stream);
 
 /* ---- bf16-operand GEMM (BASELINE configs 3 / 5: "bf16") ---------------------------------------------------------------
  * C = epilogue(op(A) . op(B)) with A, B STORED as bf16 (raw uint16 bit patterns), fp32 accumulation on

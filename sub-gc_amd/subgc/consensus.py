@@ -1,0 +1,247 @@
+"""Consensus re-ranking, method 'cider', of a whole decode batch on the device
+(misc/consensus_reranking/cr_mRNN_demo.py -> concensus_reranking_utils/consensus_reranking.py:122-179; the pair score is
+CiderScorer.compute_cider_sen_pair, external/coco_caption_patch_mRNN_cr/cider_scorer_compute_sentence.py:187-264).
+
+The reference re-ranks each image's candidate captions by the sum of their `m` largest CIDEr similarities to the captions of the image's
+`k` nearest training images -- a triple Python loop over string-keyed dictionaries, run on the captions `eval_split` wrote.  Here words
+become 16-bit ids once on the host, an n-gram is one 64-bit key, and three launches (`subgc_consensus_cook / _score / _rank`) take the
+decode loop's token rows to a per-image order.  `ConsensusCorpus` is the one-time setup (numpy / torch allowed); `ConsensusReranker.rerank`
+and the `consensus=` argument of `eval_glue.caption_images` are the per-batch path and issue only C-ABI launches.
+
+Tie rule: `np.argsort(-sim)` leaves the order of equal sums unspecified, and duplicate captions from different sub-graphs make exact
+ties routine.  The device order is STABLE: among equal sums the lower candidate index comes first.
+
+Out of scope: the nearest-image search (`find_NNimg`, a float64 cdist over ResNet features that are not shipped) -- the caller supplies
+the neighbour index lists the reference caches as `NNimg_list_*.npy`; `method='bleu'`; PTB tokenisation and the COCO metric scripts.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import ops
+from ._lib import SubgcError
+
+MAX_IDS = 65535          # word ids 1 .. 65535 (16-bit lanes of the n-gram key; 0 = no word)
+MAX_WORDS = 256          # words of one corpus caption (subgc_consensus_cook)
+MAX_CAPS = 2048          # neighbour captions per image (subgc_consensus_score)
+MAX_K = 256              # neighbour images per image
+SIGMA = 6.0              # CiderScorer's default
+
+
+def build_id_map(ref_sentences, ix_to_word):
+    """-> (word -> id, number of ids).  Model words keep the model's id (the inverse of `ix_to_word`, so a literal 'UNK' in a caption
+    is the model's UNK); words outside the vocabulary get fresh ids above it in order of first appearance: string equality and id
+    equality coincide.  More than 65535 ids are refused."""
+    word_to_ix = {}
+    for k, w in ix_to_word.items():
+        ix = int(k)
+        if ix < 1:
+            raise SubgcError(f"consensus: ix_to_word holds id {ix}; ids start at 1 (0 ends a caption)")
+        if w in word_to_ix:
+            raise SubgcError(f"consensus: ix_to_word maps both {word_to_ix[w]} and {ix} to {w!r}: ids and words must correspond one to one")
+        word_to_ix[w] = ix
+    nxt = max(word_to_ix.values(), default=0) + 1
+    for caps in ref_sentences:
+        for cap in caps:
+            for w in cap:
+                if w not in word_to_ix:
+                    word_to_ix[w] = nxt
+                    nxt += 1
+    if nxt - 1 > MAX_IDS:
+        raise SubgcError(f"consensus: the corpus needs {nxt - 1} word ids, the 16-bit n-gram lanes hold {MAX_IDS} "
+                         f"(model vocabulary {len(ix_to_word)} + {nxt - 1 - len(ix_to_word)} corpus-only words)")
+    return word_to_ix, nxt - 1
+
+
+def ngram_keys(words, woff):
+    """All n-grams (orders 1-4) of CSR sentences as uint64 keys (word j in bits 63-16j .. 48-16j) -> (keys, sentence index of each)."""
+    words = np.asarray(words, np.uint64)
+    woff = np.asarray(woff, np.int64)
+    lens = np.diff(woff)
+    sent = np.repeat(np.arange(len(lens)), lens)
+    pos = np.arange(len(words))
+    end = woff[sent + 1] if len(words) else pos
+    pad = np.concatenate([words, np.zeros(3, np.uint64)])
+    ks, ss = [], []
+    for o in range(4):
+        valid = pos + o < end
+        key = pad[pos] << np.uint64(48)
+        if o >= 1:
+            key = key | (pad[pos + 1] << np.uint64(32))
+        if o >= 2:
+            key = key | (pad[pos + 2] << np.uint64(16))
+        if o >= 3:
+            key = key | pad[pos + 3]
+        ks.append(key[valid])
+        ss.append(sent[valid])
+    return np.concatenate(ks), np.concatenate(ss)
+
+
+def gauss_table(n=MAX_WORDS, sigma=SIGMA):
+    """The length factor by |delta|, with the reference's own expression (cider_scorer_compute_sentence.py:239)."""
+    return np.array([np.e ** (-(float(d) ** 2) / (2 * sigma ** 2)) for d in range(n)], np.float64)
+
+
+class ConsensusCorpus:
+    """The reference captions of the training images (`anno_list_ref[i]['sentences']`: per image a list of captions, each a list of
+    words) as the device needs them: the id map, the sorted distinct n-gram keys with log(document frequency) -- counted per IMAGE,
+    `compute_doc_freq` -- and every caption cooked once (`subgc_consensus_cook`).  `device="auto"`: the current GPU; `device=None`: the host
+    tables only (id map, keys, log df: enough for tooling and CPU tests; `.to(device)` finishes the job later)."""
+
+    def __init__(self, ref_sentences, ix_to_word, device="auto", sigma=SIGMA):
+        self.ix_to_word = ix_to_word
+        self.word_to_ix, self.n_ids = build_id_map(ref_sentences, ix_to_word)
+        self.n_img = len(ref_sentences)
+        if self.n_img < 1:
+            raise SubgcError("consensus: an empty corpus")
+        w2i = self.word_to_ix
+        flat, lens, per_img = [], [], []
+        for caps in ref_sentences:
+            per_img.append(len(caps))
+            for cap in caps:
+                if len(cap) > MAX_WORDS:
+                    raise SubgcError(f"consensus: a corpus caption of {len(cap)} words; the limit is {MAX_WORDS}")
+                lens.append(len(cap))
+                flat.extend(w2i[w] for w in cap)
+        self.words = np.asarray(flat, np.int32)
+        self.woff = np.concatenate([[0], np.cumsum(np.asarray(lens, np.int64))]).astype(np.int64)
+        self.cap_off = np.concatenate([[0], np.cumsum(np.asarray(per_img, np.int64))]).astype(np.int64)
+        self.n_caps = len(lens)
+        self.max_words = max(lens, default=0)
+        if self.woff[-1] >= 1 << 29:
+            raise SubgcError("consensus: the corpus holds 2^29 words or more")
+        keys, sent = ngram_keys(self.words, self.woff)
+        img = np.repeat(np.arange(self.n_img), per_img)[sent] if len(sent) else sent
+        o = np.lexsort((img, keys))
+        keys, img = keys[o], img[o]
+        fresh = np.ones(len(keys), bool)
+        fresh[1:] = (keys[1:] != keys[:-1]) | (img[1:] != img[:-1])     # one count per (n-gram, image)
+        self.ukeys, df = np.unique(keys[fresh], return_counts=True)
+        self.ulogdf = np.log(np.maximum(1.0, df.astype(np.float64)))
+        self.ref_len = float(np.log(float(self.n_img)))
+        self.gauss = gauss_table(MAX_WORDS, sigma)
+        bad = np.zeros(max((int(k) for k in ix_to_word), default=0) + 1, np.uint8)
+        from .eval_glue import BAD_ENDINGS
+        for k, w in ix_to_word.items():
+            if w in BAD_ENDINGS:
+                bad[int(k)] = 1
+        self.bad = bad
+        self.device = None
+        if device == "auto":
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device is not None:
+            self.to(device)
+
+    def to(self, device):
+        """Upload the tables and cook every corpus caption (one launch); done once."""
+        dev = torch.device(device)
+        self.d_words = torch.from_numpy(self.words).to(dev)
+        self.d_woff = torch.from_numpy(self.woff.astype(np.int32)).to(dev)
+        self.d_cap_off = torch.from_numpy(self.cap_off.astype(np.int32)).to(dev)
+        self.d_ukeys = torch.from_numpy(self.ukeys.view(np.int64)).to(dev)
+        self.d_ulogdf = torch.from_numpy(self.ulogdf).to(dev)
+        self.d_gauss = torch.from_numpy(self.gauss).to(dev)
+        self.d_bad = torch.from_numpy(self.bad).to(dev)
+        self.cooked = ops.consensus_cook(self.d_words, self.d_ukeys, self.d_ulogdf, self.ref_len, woff=self.d_woff, max_words=self.max_words)
+        self.device = dev
+        return self
+
+    def encode(self, words):
+        """A caption (list of words, or a string) -> ids; words the corpus never saw and the model does not know get id 0 -> refused."""
+        if isinstance(words, str):
+            words = words.split()
+        try:
+            return [self.word_to_ix[w] for w in words]
+        except KeyError as e:
+            raise SubgcError(f"consensus: word {e.args[0]!r} is neither in the model's vocabulary nor in the corpus") from None
+
+
+class ConsensusReranker:
+    """`consensus_rerank(method='cider')` for a decode batch: candidates = the (sGPN-ranked) token rows of each image, neighbours = the
+    first `k` entries of the image's nearest-training-image list, score = sum of the `m` largest pair scores (defaults k_cider = 60,
+    m_cider = 125 of cr_mRNN_demo.py)."""
+
+    def __init__(self, corpus, k=60, m=125):
+        if m < 1:
+            raise SubgcError(f"consensus: m = {m}; at least one pair score is summed")
+        if not 1 <= k <= MAX_K:
+            raise SubgcError(f"consensus: k = {k}; 1 <= k <= {MAX_K} neighbour images")
+        self.corpus, self.k, self.m = corpus, int(k), int(m)
+
+    def neighbours(self, nn_lists):
+        """-> (int32 [I, k] array of the first k neighbours, the largest neighbour-caption count of an image); host work, numpy."""
+        k, c = self.k, self.corpus
+        for j, l in enumerate(nn_lists):
+            if len(l) < k:
+                raise SubgcError(f"consensus: k = {k} is larger than the neighbour list of image {j} ({len(l)} entries)")
+        nn = np.asarray([np.asarray(l[:k], np.int64) for l in nn_lists], np.int64).reshape(len(nn_lists), k)
+        cl = np.clip(nn, 0, c.n_img - 1)                                    # what the kernel reads for an index out of range
+        caps = (c.cap_off[cl + 1] - c.cap_off[cl]).sum(1)
+        max_caps = int(caps.max()) if len(caps) else 0
+        if max_caps > MAX_CAPS:
+            raise SubgcError(f"consensus: image {int(caps.argmax())} has {max_caps} neighbour captions; the limit is {MAX_CAPS} per image")
+        return nn.astype(np.int32), max_caps
+
+    def enqueue(self, seq, seg, I, max_rows, nn_lists, top_k, remove_bad_endings, sim, order, first=None, pair_out=None):
+        """The three launches on the current stream.  seq: device token rows [rows, T] (int32 / int64) in candidate order; seg: device
+        int32 row boundaries (>= I + 1 entries); sim fp64 [rows], order int32 [rows], first int32 [I]: device outputs."""
+        c = self.corpus
+        if c.device is None:
+            raise SubgcError("consensus: the corpus is not on a device (ConsensusCorpus(..., device=...) or .to(device))")
+        if len(nn_lists) != I:
+            raise SubgcError("consensus: one neighbour list per image")
+        T = seq.size(1)
+        top_k = 0 if top_k is None else int(top_k)
+        if top_k < 0:
+            raise SubgcError("consensus: top_k >= 1 or None")
+        nn, max_caps = self.neighbours(nn_lists)
+        d_nn = torch.from_numpy(nn).to(seq.device)
+        cand = ops.consensus_cook(seq, c.d_ukeys, c.d_ulogdf, c.ref_len, bad=c.d_bad if remove_bad_endings else None)
+        ops.consensus_score(cand, T, seg, I, max_rows, top_k, d_nn, self.k, c.d_cap_off, c.n_img, c.n_caps, c.d_woff, c.cooked, c.d_gauss,
+                            self.m, max_caps, sim, pair_out)
+        ops.consensus_rank(sim, seg, I, top_k, order, first)
+        return max_caps
+
+    def rerank(self, seq, bounds, nn_lists, top_k=None, remove_bad_endings=0, return_pairs=False):
+        """seq [rows, T]: the decode batch's device token rows, image i owning rows bounds[i] .. bounds[i+1]-1 in sGPN-ranked order;
+        top_k keeps each image's first top_k rows (cr_mRNN_demo.py --top_k; None: all).
+        -> (order, sim): per image an int64 array (indices into the image's candidate list, best first; equal sums: lower index first)
+        and the fp64 sums of its candidates; with return_pairs also the per-image [candidates, neighbour captions] pair scores."""
+        if not seq.is_cuda:
+            raise SubgcError("subgc ops need device tensors (the HIP path has no CPU fallback)")
+        rows, I = seq.size(0), len(bounds) - 1
+        if bounds[-1] != rows:
+            raise SubgcError("consensus: bounds do not cover the rows of seq")
+        dev = seq.device
+        sizes = [b - a for a, b in zip(bounds, bounds[1:])]
+        max_rows = max(sizes + [0])
+        if rows == 0 or I == 0:
+            return [np.zeros(0, np.int64) for _ in range(I)], [np.zeros(0, np.float64) for _ in range(I)]
+        seg = ops.upload(list(bounds), torch.int32, dev)
+        arena = torch.empty(3 * rows, device=dev, dtype=torch.int32)
+        sim, order = arena[:2 * rows].view(torch.float64), arena[2 * rows:]
+        pairs = None
+        if return_pairs:
+            _, mc = self.neighbours(nn_lists)
+            pairs = torch.empty(rows, max(mc, 1), device=dev, dtype=torch.float64)
+        self.enqueue(seq.contiguous(), seg, I, max_rows, nn_lists, top_k, remove_bad_endings, sim, order, None, pairs)
+        host = arena.cpu().numpy()                                          # the one copy
+        h_sim, h_order = host[:2 * rows].view(np.float64), host[2 * rows:]
+        keep = [n if not top_k else min(n, int(top_k)) for n in sizes]
+        out_o = [h_order[a:a + n].astype(np.int64) for a, n in zip(bounds, keep)]
+        out_s = [h_sim[a:a + n].copy() for a, n in zip(bounds, keep)]
+        if return_pairs:
+            hp = pairs.cpu().numpy()
+            return out_o, out_s, [hp[a:a + n] for a, n in zip(bounds, keep)]
+        return out_o, out_s
+
+
+def save_rerank_ind(path, rerank_ind):
+    """Write {image_id: order} in the format of the reference's `consensus_rerank_ind.npy` (consensus_reranking.py:174,179: a pickled
+    dict of python lists, read back by misc/grd_utils.py:34 with `np.load(..., allow_pickle=True).tolist()`)."""
+    np.save(path, {k: [int(x) for x in v] for k, v in rerank_ind.items()})
+
+
+def load_rerank_ind(path):
+    return np.load(path, allow_pickle=True, encoding="latin1").tolist()

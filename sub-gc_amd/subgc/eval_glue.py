@@ -62,7 +62,7 @@ def rank_subgraphs(model, seqq, subgraph_score, keep_nms_ind, sct_mode=False):
 
 
 @torch.no_grad()
-def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256, shard=False, grd_pick=None):
+def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256, shard=False, grd_pick=None, consensus=None):
     """The testing branch of eval_split for a list of loader items: returns the `predictions` list
     (eval_utils.py:132-141): {'image_id', 'caption': [...], 'subgraph_score', 'sorted_subgraph_ind'} per image.
 
@@ -77,7 +77,15 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
     `eval_kwargs["return_att"] = 1` (the grounding experiments, eval_utils.py:98-101,143-146): every entry also gets
     `"grounding"`: {'subg_index', 'sort_ind', 'att2_ind', 'node_ind'} -- for the caption ranked `subg_index` (0 = best by sGPN score;
     `grd_pick[i]` = the consensus re-ranker's choice for image i, grd_utils.py:31-35) the arg-max attention column of every word
-    position and the full-graph node id (= box row) it stands for (grd_utils.py:36-47; `grounding_material` finishes the entry)."""
+    position and the full-graph node id (= box row) it stands for (grd_utils.py:36-47; `grounding_material` finishes the entry).
+
+    `consensus={"reranker": ConsensusReranker, "nn": {image_id: [nearest training-image indices]}, "top_k": 4}` (default None: off)
+    re-ranks every image's sGPN-sorted captions -- its best `top_k`, None = all -- by CIDEr consensus on the device, in the decode
+    batch's own pass (subgc.consensus; cr_mRNN_demo.py -> consensus_rerank).  Every entry gains `"consensus_rerank_ind"` (indices into
+    its `caption` list, best first, equal sums in ascending index: what the reference's consensus_rerank_ind.npy holds) and
+    `"consensus_sim"` (the fp64 sums of those captions).  With `return_att` the grounding entry is the re-ranker's FIRST choice, picked on
+    the device in the same pass -- no second evaluation run; an explicit `grd_pick` still wins.  `remove_bad_endings` trims the
+    candidates exactly as it trims the strings.  Not available in `sct` mode."""
     import torch.distributed as dist
     from . import parallel
     eval_kwargs = dict(eval_kwargs or {})
@@ -93,13 +101,20 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                              f"(rank {dist.get_rank()} has {len(ids)} images, the ranks hold {[len(s) for s in seen]})")
         mine, idx = parallel.shard_images(images, dist.get_rank(), world)
         local = caption_images(model, mine, [infos[i] for i in idx], ix_to_word, eval_kwargs, group, shard=False,
-                               grd_pick=None if grd_pick is None else [grd_pick[i] for i in idx])
+                               grd_pick=None if grd_pick is None else [grd_pick[i] for i in idx], consensus=consensus)
         return parallel.gather_by_index(local, idx, len(images))
     sct_mode = eval_kwargs.get("sct", 0) == 1
     rbe = eval_kwargs.get("remove_bad_endings", 0)
     return_att = eval_kwargs.get("return_att", 0) == 1
     if grd_pick is not None and len(grd_pick) != len(images):
         raise ValueError("caption_images: one grd_pick entry per image")
+    if consensus is not None:
+        if sct_mode:
+            raise ValueError("caption_images: consensus re-ranking is not defined in sct (controllability) mode: its captions keep the "
+                             "input order and are not ranked")
+        missing = [info["id"] for info in infos if info["id"] not in consensus["nn"]]
+        if missing:
+            raise ValueError(f"caption_images: consensus['nn'] has no neighbour list for image ids {missing[:5]}")
     was_training = model.training
     model.eval()
     predictions = []
@@ -111,6 +126,8 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
             chunk, chunk_infos = images[i:i + group], infos[i:i + group]
             hold = {"skip_att": True}
             results = model.sample_images(chunk, opt=eval_kwargs) if sct_mode else _sample_batch(model, chunk, eval_kwargs, hold)
+            if "bounds" not in hold and consensus is not None:
+                raise ValueError("caption_images: consensus re-ranking needs a model whose sample_images exposes the decode batch (batch_out)")
             if "bounds" not in hold:
                 # per image: controllability mode (input order, first half, no ranking; rare) and models whose sample_images does not
                 # expose the batch tensors
@@ -124,18 +141,29 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                 for info in chunk_infos:
                     predictions.append({"image_id": info["id"], "caption": [], "subgraph_score": np.zeros(0, np.float32),
                                         "sorted_subgraph_ind": np.zeros(0, np.int64)})
+                    if consensus is not None:
+                        predictions[-1].update(consensus_rerank_ind=np.zeros(0, np.int64), consensus_sim=np.zeros(0, np.float64))
                 continue
             ground = return_att and hold.get("AL") is not None
             pick = None if grd_pick is None else grd_pick[i:i + group]
             # eval_utils.py:105-115 for every image of the batch + grd_utils.py:36-47: two launches, one host copy
             h = ops.eval_collect(hold["score"], hold["keep"], hold["seq"], bounds, identity=not model.gpn,
-                                 AL=hold["AL"] if ground else None, idx=hold["idx"] if ground else None, pick=pick if ground else None)
+                                 AL=hold["AL"] if ground else None, idx=hold["idx"] if ground else None, pick=pick if ground else None,
+                                 consensus=None if consensus is None else {
+                                     "reranker": consensus["reranker"], "nn": [consensus["nn"][info["id"]] for info in chunk_infos],
+                                     "top_k": consensus.get("top_k"), "remove_bad_endings": rbe})
+            ctk = None if consensus is None else consensus.get("top_k")
             for j, (info, a, b) in enumerate(zip(chunk_infos, bounds, bounds[1:])):
                 entry = {"image_id": info["id"], "caption": decode_sequence(ix_to_word, h["seq"][a:b], rbe),
                          "subgraph_score": h["score"][a:b], "sorted_subgraph_ind": h["keep"][a:b]}
+                if consensus is not None:
+                    nc = (b - a) if not ctk else min(b - a, int(ctk))
+                    entry["consensus_rerank_ind"] = h["c_order"][a:a + nc].astype(np.int64)
+                    entry["consensus_sim"] = h["c_sim"][a:a + nc].copy()
                 if ground:
                     w = int(h["n_words"][j])
-                    entry["grounding"] = {"subg_index": 0 if pick is None else int(pick[j]), "sort_ind": h["order"][a:b],
+                    sub = int(pick[j]) if pick is not None else (int(h["c_first"][j]) if consensus is not None else 0)
+                    entry["grounding"] = {"subg_index": sub, "sort_ind": h["order"][a:b],
                                           "att2_ind": h["att2"][j, :w].astype(np.int64), "node_ind": h["node"][j, :w].astype(np.int64)}
                 predictions.append(entry)
     finally:

@@ -1471,13 +1471,17 @@ def rank_desc(score):
     return srt, order
 
 
-def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pick=None):
+def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pick=None, consensus=None):
     """The eval loop's per-image work for a whole decode batch (misc/eval_utils.py:105-121; grounding: misc/grd_utils.py:36-47):
     one ranking launch (subgc_eval_rank_rows), one grounding launch when `AL` (the decode loop's attention buffer [T1, rows, N]) and
     `idx` (the kept sub-graphs' node lists [rows, N]) are given, and ONE device -> host copy of everything.
     score [rows] fp32, keep [rows] int64, seq [rows, T] int64, bounds: python list of the I + 1 row boundaries of the images,
     pick: optional per-image subg_index list (default 0 = the best-ranked caption).
-    -> dict of host numpy arrays: order / score / keep (int64) / seq (int64) [rows...], and with grounding att2 / node [I, T1], n_words [I]."""
+    consensus: optional {"reranker": ConsensusReranker, "nn": per-image neighbour index lists, "top_k": int or None, "remove_bad_endings": 0 / 1}:
+    the ranked token rows are re-ranked on the device in the same pass (subgc_consensus_cook / _score / _rank) and, unless `pick` is
+    given, the grounding launch takes each image's pick from the re-ranker's first choice ON THE DEVICE; its outputs ride in the same copy.
+    -> dict of host numpy arrays: order / score / keep (int64) / seq (int64) [rows...], and with grounding att2 / node [I, T1], n_words [I];
+    with consensus c_order (int32 [rows]: image i's order in its first n_i' = min(n_i, top_k) slots), c_sim (fp64 [rows]), c_first [I]."""
     import numpy as np
     dev = score.device
     rows, T = seq.shape
@@ -1488,6 +1492,9 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
     T1 = AL.size(0) if ground else 0
     seg = upload(list(bounds) + ([0] * I if pick is None else [int(p) for p in pick]), torch.int32, dev)
     words = 3 * rows + rows * T + (2 * I * T1 + I if ground else 0)
+    o_cons = (words + 1) & ~1                                         # the fp64 sums need an 8-byte aligned slot
+    if consensus is not None:
+        words = o_cons + 3 * rows + I
     arena = torch.empty(max(words, 1), device=dev, dtype=torch.int32)
     o = 0
     order = arena[o:o + rows]; o += rows
@@ -1498,6 +1505,14 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
     if I and rows:
         call("subgc_eval_rank_rows", _ptr(score.contiguous(), torch.float32), _ptr(keep.contiguous(), torch.int64), _ptr(seq.contiguous(), torch.int64),
              T, _ptr(seg), I, max_rows, int(bool(identity)), _ptr(order), _ptr(score_s), _ptr(keep_s), _ptr(seq_s), _stream())
+    c_first = None
+    if consensus is not None:
+        c_sim = arena[o_cons:o_cons + 2 * rows].view(torch.float64)
+        c_order = arena[o_cons + 2 * rows:o_cons + 3 * rows]
+        c_first = arena[o_cons + 3 * rows:o_cons + 3 * rows + I]
+        if I and rows:
+            consensus["reranker"].enqueue(seq_s.view(rows, T), seg, I, max_rows, consensus["nn"], consensus.get("top_k"),
+                                          consensus.get("remove_bad_endings", 0), c_sim, c_order, c_first)
     if ground:
         att2 = arena[o:o + I * T1]; o += I * T1
         node = arena[o:o + I * T1]; o += I * T1
@@ -1507,7 +1522,8 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
         if I:
             call("subgc_grounding_argmax", _ptr(AL, torch.float32), AL.stride(0), AL.stride(1), AL.size(2), T1, _ptr(seq.contiguous(), torch.int64), T,
                  _ptr(idx, torch.int64), idx.stride(0), _ptr(seg), _ptr(order) if (rows and not identity) else None,
-                 _ptr(seg[I + 1:]) if pick is not None else None, I, _ptr(att2), _ptr(node), _ptr(nw), _stream())
+                 _ptr(seg[I + 1:]) if pick is not None else (_ptr(c_first) if (c_first is not None and rows) else None), I, _ptr(att2), _ptr(node),
+                 _ptr(nw), _stream())
     host = arena.cpu().numpy()                                        # the one copy (synchronises the stream)
     o = 0
     out = {"order": host[o:o + rows].astype(np.int64)}; o += rows
@@ -1518,7 +1534,55 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
         out["att2"] = host[o:o + I * T1].reshape(I, T1).copy(); o += I * T1
         out["node"] = host[o:o + I * T1].reshape(I, T1).copy(); o += I * T1
         out["n_words"] = host[o:o + I].copy()
+    if consensus is not None:
+        out["c_sim"] = host[o_cons:o_cons + 2 * rows].view(np.float64).copy()
+        out["c_order"] = host[o_cons + 2 * rows:o_cons + 3 * rows].copy()
+        out["c_first"] = host[o_cons + 3 * rows:o_cons + 3 * rows + I].copy()
     return out
+
+
+def consensus_cook(tok, ukeys, ulogdf, ref_len, woff=None, max_words=0, row_len=None, bad=None):
+    """subgc_consensus_cook: sentences -> sorted (n-gram key, tf-idf weight) lists, norms and bigram lengths (precook + counts2vec,
+    cider_scorer_compute_sentence.py:15-30,188-212).  tok: int32 / int64; CSR over `woff` (int32 [S + 1], at most `max_words` words per
+    sentence) or token rows [S, T] (words before the first 0, at most row_len[s], minus trailing `bad` words).
+    -> (keys int64 bit patterns, wts fp64, cnt int32 [S], blen int32 [S], norm fp64 [S, 4]); sentence s owns keys / wts [4 * first word ...)."""
+    p_tok = _ptr(tok)
+    if tok.dtype not in (torch.int32, torch.int64) or not tok.is_contiguous():
+        raise SubgcError(f"consensus_cook: contiguous int32 / int64 tokens, got {tok.dtype}")
+    if woff is not None:
+        S, T = woff.numel() - 1, 0
+    else:
+        S, T = tok.shape
+    dev = tok.device
+    keys = torch.empty(max(4 * tok.numel(), 1), device=dev, dtype=torch.int64)
+    wts = torch.empty(max(4 * tok.numel(), 1), device=dev, dtype=torch.float64)
+    cnt = torch.empty(max(S, 1), device=dev, dtype=torch.int32)
+    blen = torch.empty(max(S, 1), device=dev, dtype=torch.int32)
+    norm = torch.empty(max(S, 1), 4, device=dev, dtype=torch.float64)
+    call("subgc_consensus_cook", p_tok, int(tok.dtype == torch.int64), _ptr(woff, torch.int32), int(T), _ptr(row_len, torch.int32),
+         _ptr(bad, torch.uint8), 0 if bad is None else bad.numel(), int(S), int(max_words), _ptr(ukeys, torch.int64), _ptr(ulogdf, torch.float64),
+         ukeys.numel(), float(ref_len), _ptr(keys), _ptr(wts), _ptr(cnt), _ptr(blen), _ptr(norm), _stream())
+    return keys, wts, cnt, blen, norm
+
+
+def consensus_score(cand, T, seg, I, max_cand, top_k, nn, k, cap_off, n_img, n_caps, nwoff, corpus, gauss, m, max_caps, sim, pair_out=None):
+    """subgc_consensus_score: sim[row] = sum of the m largest CIDEr pair scores of candidate `row` against its image's neighbour captions
+    (consensus_reranking.py:155-169).  cand / corpus: the tuples consensus_cook returned (rows of width T / CSR over nwoff); nn int32 [I, >= k]."""
+    ck, cw, cc, cl, cn = cand
+    nk, nw, nc, nl, nno = corpus
+    call("subgc_consensus_score", _ptr(ck, torch.int64), _ptr(cw, torch.float64), _ptr(cc, torch.int32), _ptr(cl, torch.int32), _ptr(cn, torch.float64),
+         int(T), _ptr(seg, torch.int32), int(I), int(max_cand), int(top_k), _ptr(nn, torch.int32), nn.stride(0) if nn.dim() == 2 else nn.numel(), int(k),
+         _ptr(cap_off, torch.int32), int(n_img), int(n_caps), _ptr(nwoff, torch.int32), _ptr(nk, torch.int64), _ptr(nw, torch.float64),
+         _ptr(nc, torch.int32), _ptr(nl, torch.int32), _ptr(nno, torch.float64), _ptr(gauss, torch.float64), gauss.numel(), int(m), int(max_caps),
+         _ptr(sim, torch.float64), _ptr(pair_out, torch.float64), 0 if pair_out is None else pair_out.stride(0), _stream())
+    return sim
+
+
+def consensus_rank(sim, seg, I, top_k, order, first=None):
+    """subgc_consensus_rank: per image the stable descending order of the fp64 sums (ties: lower candidate index first) and its head."""
+    call("subgc_consensus_rank", _ptr(sim, torch.float64), _ptr(seg, torch.int32), int(I), int(top_k), _ptr(order, torch.int32),
+         _ptr(first, torch.int32), _stream())
+    return order
 
 
 def dropout_mask(shape, p, seed, offset, device):
