@@ -3,7 +3,7 @@
  *
  * The reference (YiwuZhong/Sub-GC) has no FFI layer: its hot path is ATen calls made from
  * models/AttModel.py, models/lib/{gcn_backbone,graph_conv,graph_conv_unit,gpn}.py and
- * misc/utils.py.  Each of the 130 entry points below replaces the op site cited next to it (file:line in
+ * misc/utils.py.  Each of the 133 entry points below replaces the op site cited next to it (file:line in
  * /root/reference).  INTEGRATION.md shows the ctypes binding a maintainer adds.
  *
  * Contract for EVERY function:
@@ -762,6 +762,60 @@ int subgc_consensus_score(const uint64_t* ckeys, const double* cw, const int32_t
                           const int32_t* ncnt, const int32_t* nlen, const double* nnorm, const double* gauss, int n_gauss, int m,
                           int max_caps, double* sim, double* pair_out, int64_t pair_ld, void* stream);
 int subgc_consensus_rank(const double* sim, const int32_t* seg, int I, int top_k, int32_t* order, int32_t* first, void* stream);
+
+/* Diversity scores (misc/diversity/diversity_score.py:55-163; the sentence BLEU-4 of metric 4 is misc/diversity/bleu_scorer.py:26-93 and
+ * :248-256, reached through cal_avg_B4, diversity_score.py:36-53) for a whole decode batch.  Image i owns rows seg[i] .. seg[i+1]-1 of
+ * tok [rows, T] (int32, or int64 with tok64 != 0; T <= 64) and of score [rows] (fp32), in sGPN-ranked order.  A SET s is the image
+ * set_img[s] plus a DRAW, the script's `rand_ind`: the image-LOCAL row indices draw[set_off[s] .. set_off[s+1]) (int32, n_draw entries in
+ * all, at most max_draw <= 1024 per set -- the caller states the largest length, what lies beyond it is not read).  The draws are an
+ * input: the script takes them from one host random stream that runs over the whole file.  One workgroup per set; none needs scratch.
+ * A caption is the ids of its row before the first id <= 0; with bad != NULL (uint8 [bad_n]) without its trailing words w with
+ * bad[w] != 0 unless every word is one (decode_sequence's REMOVE_BAD_ENDINGS rule, misc/utils.py:74-80, as subgc_consensus_cook).  Words
+ * are 16-bit ids and n-grams 64-bit keys as in the consensus family: every comparison is exact.
+ * Results: set s owns out_i[s * ld_i ...] (int32: the SUBGC_DIV_* columns, then its selection, ld_i >= SUBGC_DIV_SEL + n_best) and
+ * out_d[s * ld_d ...] (fp64: n_best sentence values, then their mean, ld_d >= n_best + 1).  set_flags[s] (SUBGC_DIV_WANT_*) names what
+ * the set is for; columns a set does not want are written as 0.
+ *
+ * subgc_diversity_select (:63-65, `rand_ind[np.argsort(score[rand_ind])[::-1][:5]]`): SUBGC_DIV_SELECTED = min(draw length, n_best),
+ * 2 <= n_best <= 16, and out_i[SUBGC_DIV_SEL + r] = the image-local row of the r-th best score of the draw (-1 past the count).  Scores
+ * are compared as order-preserving integer keys (-0 = +0).  EQUAL scores: the row LATER in the draw comes first -- a stable ascending
+ * sort, reversed; numpy's default argsort leaves the order of equal scores open, so this rule is this library's.
+ * subgc_diversity_distinct (metric 1, :154-160; sets with SUBGC_DIV_WANT_DRAW): SUBGC_DIV_DRAWN = the draw's length, SUBGC_DIV_DISTINCT =
+ * its distinct captions.  A 64-bit hash of the ids pre-filters; equal hashes are confirmed on the tokens.
+ * subgc_diversity_best, over the rows subgc_diversity_select left in out_i:
+ *   SUBGC_DIV_WANT_WORDS (metric 3, :96-108; metric 2, :143-145): SUBGC_DIV_WORDS = total words with `split(' ')`'s rule that an empty
+ *   caption is ONE word, the empty word; SUBGC_DIV_UNIGRAMS / _BIGRAMS = distinct words / distinct within-sentence word pairs;
+ *   SUBGC_DIV_NOVEL = selected captions absent from the training-caption index (nv_off NULL: 0): nv_n DISTINCT captions in
+ *   lexicographic order of their id lists (a prefix first), caption c = nv_tok[nv_off[c] .. nv_off[c+1]) -- binary search, each step a
+ *   comparison of the id lists themselves.
+ *   SUBGC_DIV_WANT_BLEU (metric 4, :67-79): out_d[q] = BLEU-4 of selected sentence q against the other selected ones -- matches clipped
+ *   by the maximum count over the references (cook_refs / cook_test, `split()`: an empty caption has no words), reference length the
+ *   closest, the shorter on a tie, then bleu_scorer.py:248-256 in fp64 and in that order: the running product of
+ *   (correct + 1e-15) / (guess + 1e-9), ** (1/4), times exp(1 - 1/ratio) when ratio < 1; out_d[n_best] = their mean, summed in
+ *   np.mean's order; SUBGC_DIV_VALID = 1.  A selection of fewer than 2 sentences (the reference asserts there, bleu.py:38):
+ *   SUBGC_DIV_VALID = 0 and zeros.
+ * Indices are clamped into the buffers (set_img into [0, I), seg into [0, rows], draw entries into the image's rows); debug bounds mode
+ * reports a set_img outside [0, I), a seg that is not monotone inside [0, rows] and a draw entry outside its image's rows instead.  */
+#define SUBGC_DIV_DRAWN 0
+#define SUBGC_DIV_DISTINCT 1
+#define SUBGC_DIV_SELECTED 2
+#define SUBGC_DIV_WORDS 3
+#define SUBGC_DIV_UNIGRAMS 4
+#define SUBGC_DIV_BIGRAMS 5
+#define SUBGC_DIV_NOVEL 6
+#define SUBGC_DIV_VALID 7
+#define SUBGC_DIV_SEL 8
+#define SUBGC_DIV_WANT_DRAW 1
+#define SUBGC_DIV_WANT_WORDS 2
+#define SUBGC_DIV_WANT_BLEU 4
+int subgc_diversity_select(const float* score, const int32_t* seg, int I, int rows, const int32_t* set_img, const int32_t* set_off,
+                           const int32_t* draw, int n_sets, int n_draw, int max_draw, int n_best, int32_t* out_i, int ld_i, void* stream);
+int subgc_diversity_distinct(const void* tok, int tok64, int T, const uint8_t* bad, int bad_n, const int32_t* seg, int I, int rows,
+                             const int32_t* set_img, const int32_t* set_off, const int32_t* set_flags, const int32_t* draw, int n_sets,
+                             int n_draw, int max_draw, int32_t* out_i, int ld_i, void* stream);
+int subgc_diversity_best(const void* tok, int tok64, int T, const uint8_t* bad, int bad_n, const int32_t* seg, int I, int rows,
+                         const int32_t* set_img, const int32_t* set_flags, int n_sets, int n_best, const int32_t* nv_off,
+                         const int32_t* nv_tok, int nv_n, int32_t* out_i, int ld_i, double* out_d, int ld_d, void* stream);
 
 /* ---- bf16-operand GEMM (BASELINE configs 3 / 5: "bf16") ---------------------------------------------------------------
  * C = epilogue(op(A) . op(B)) with A, B STORED as bf16 (raw uint16 bit patterns), fp32 accumulation on

@@ -62,7 +62,7 @@ def rank_subgraphs(model, seqq, subgraph_score, keep_nms_ind, sct_mode=False):
 
 
 @torch.no_grad()
-def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256, shard=False, grd_pick=None, consensus=None):
+def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256, shard=False, grd_pick=None, consensus=None, diversity=None):
     """The testing branch of eval_split for a list of loader items: returns the `predictions` list
     (eval_utils.py:132-141): {'image_id', 'caption': [...], 'subgraph_score', 'sorted_subgraph_ind'} per image.
 
@@ -85,7 +85,15 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
     its `caption` list, best first, equal sums in ascending index: what the reference's consensus_rerank_ind.npy holds) and
     `"consensus_sim"` (the fp64 sums of those captions).  With `return_att` the grounding entry is the re-ranker's FIRST choice, picked on
     the device in the same pass -- no second evaluation run; an explicit `grd_pick` still wins.  `remove_bad_endings` trims the
-    candidates exactly as it trims the strings.  Not available in `sct` mode."""
+    candidates exactly as it trims the strings.  Not available in `sct` mode.
+
+    `diversity={"scorer": DiversityScorer, "top_n": (20, 100), "seed": 2019}` (default None: off) scores every image's captions the way
+    misc/diversity/diversity_score.py does -- distinct captions of a random draw, n-gram diversity, novel captions and mBLEU-4 of the
+    draw's best five by sGPN score -- on the device, in the decode batch's own pass and its one copy (subgc.diversity).  Every entry gains
+    `"diversity"`: plain integer counts and fp64 values with one entry per `top_n` (`DiversityScorer.unpack`); `diversity.summarize` of
+    those entries gives the numbers the script prints.  The draws come from `per_image_draws`, keyed by the image id, so `group`, the
+    order of the list and `shard=True` cannot change an image's result (the script's own stream runs over the whole file;
+    `diversity.score_predictions` reproduces that one).  Works together with `consensus=`; not available in `sct` mode."""
     import torch.distributed as dist
     from . import parallel
     eval_kwargs = dict(eval_kwargs or {})
@@ -101,7 +109,7 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                              f"(rank {dist.get_rank()} has {len(ids)} images, the ranks hold {[len(s) for s in seen]})")
         mine, idx = parallel.shard_images(images, dist.get_rank(), world)
         local = caption_images(model, mine, [infos[i] for i in idx], ix_to_word, eval_kwargs, group, shard=False,
-                               grd_pick=None if grd_pick is None else [grd_pick[i] for i in idx], consensus=consensus)
+                               grd_pick=None if grd_pick is None else [grd_pick[i] for i in idx], consensus=consensus, diversity=diversity)
         return parallel.gather_by_index(local, idx, len(images))
     sct_mode = eval_kwargs.get("sct", 0) == 1
     rbe = eval_kwargs.get("remove_bad_endings", 0)
@@ -115,6 +123,12 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
         missing = [info["id"] for info in infos if info["id"] not in consensus["nn"]]
         if missing:
             raise ValueError(f"caption_images: consensus['nn'] has no neighbour list for image ids {missing[:5]}")
+    if diversity is not None:
+        if sct_mode:
+            raise ValueError("caption_images: diversity scores are not defined in sct (controllability) mode: its captions keep the input "
+                             "order and are not ranked")
+        from .diversity import TOP_N, per_image_draws
+        d_scorer, d_top_n, d_seed = diversity["scorer"], tuple(diversity.get("top_n", TOP_N)), diversity.get("seed", 2019)
     was_training = model.training
     model.eval()
     predictions = []
@@ -128,6 +142,8 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
             results = model.sample_images(chunk, opt=eval_kwargs) if sct_mode else _sample_batch(model, chunk, eval_kwargs, hold)
             if "bounds" not in hold and consensus is not None:
                 raise ValueError("caption_images: consensus re-ranking needs a model whose sample_images exposes the decode batch (batch_out)")
+            if "bounds" not in hold and diversity is not None:
+                raise ValueError("caption_images: diversity scores need a model whose sample_images exposes the decode batch (batch_out)")
             if "bounds" not in hold:
                 # per image: controllability mode (input order, first half, no ranking; rare) and models whose sample_images does not
                 # expose the batch tensors
@@ -137,12 +153,21 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                                         "subgraph_score": score.cpu().numpy(), "sorted_subgraph_ind": sorted_ind.cpu().numpy()})
                 continue
             bounds = hold["bounds"]
+            div = None
+            if diversity is not None:
+                sizes = [b - a for a, b in zip(bounds, bounds[1:])]
+                d_plan = d_scorer.plan(per_image_draws(sizes, [info["id"] for info in chunk_infos], d_top_n, d_seed), sizes)
+                div = {"scorer": d_scorer, "plan": d_plan, "remove_bad_endings": rbe}
             if hold["rows"] == 0:
-                for info in chunk_infos:
+                d_none = None if div is None else d_scorer.unpack(d_plan, np.zeros((d_plan["n_sets"], ops.DIV_COLS + d_scorer.n_best), np.int32),
+                                                                  np.zeros((d_plan["n_sets"], d_scorer.n_best + 1)), d_top_n)
+                for j, info in enumerate(chunk_infos):
                     predictions.append({"image_id": info["id"], "caption": [], "subgraph_score": np.zeros(0, np.float32),
                                         "sorted_subgraph_ind": np.zeros(0, np.int64)})
                     if consensus is not None:
                         predictions[-1].update(consensus_rerank_ind=np.zeros(0, np.int64), consensus_sim=np.zeros(0, np.float64))
+                    if div is not None:
+                        predictions[-1]["diversity"] = d_none[j]
                 continue
             ground = return_att and hold.get("AL") is not None
             pick = None if grd_pick is None else grd_pick[i:i + group]
@@ -151,7 +176,8 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                                  AL=hold["AL"] if ground else None, idx=hold["idx"] if ground else None, pick=pick if ground else None,
                                  consensus=None if consensus is None else {
                                      "reranker": consensus["reranker"], "nn": [consensus["nn"][info["id"]] for info in chunk_infos],
-                                     "top_k": consensus.get("top_k"), "remove_bad_endings": rbe})
+                                     "top_k": consensus.get("top_k"), "remove_bad_endings": rbe}, diversity=div)
+            d_entries = None if div is None else d_scorer.unpack(d_plan, h["d_int"], h["d_f64"], d_top_n)
             ctk = None if consensus is None else consensus.get("top_k")
             for j, (info, a, b) in enumerate(zip(chunk_infos, bounds, bounds[1:])):
                 entry = {"image_id": info["id"], "caption": decode_sequence(ix_to_word, h["seq"][a:b], rbe),
@@ -160,6 +186,8 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                     nc = (b - a) if not ctk else min(b - a, int(ctk))
                     entry["consensus_rerank_ind"] = h["c_order"][a:a + nc].astype(np.int64)
                     entry["consensus_sim"] = h["c_sim"][a:a + nc].copy()
+                if div is not None:
+                    entry["diversity"] = d_entries[j]
                 if ground:
                     w = int(h["n_words"][j])
                     sub = int(pick[j]) if pick is not None else (int(h["c_first"][j]) if consensus is not None else 0)

@@ -1471,7 +1471,7 @@ def rank_desc(score):
     return srt, order
 
 
-def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pick=None, consensus=None):
+def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pick=None, consensus=None, diversity=None):
     """The eval loop's per-image work for a whole decode batch (misc/eval_utils.py:105-121; grounding: misc/grd_utils.py:36-47):
     one ranking launch (subgc_eval_rank_rows), one grounding launch when `AL` (the decode loop's attention buffer [T1, rows, N]) and
     `idx` (the kept sub-graphs' node lists [rows, N]) are given, and ONE device -> host copy of everything.
@@ -1481,7 +1481,10 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
     the ranked token rows are re-ranked on the device in the same pass (subgc_consensus_cook / _score / _rank) and, unless `pick` is
     given, the grounding launch takes each image's pick from the re-ranker's first choice ON THE DEVICE; its outputs ride in the same copy.
     -> dict of host numpy arrays: order / score / keep (int64) / seq (int64) [rows...], and with grounding att2 / node [I, T1], n_words [I];
-    with consensus c_order (int32 [rows]: image i's order in its first n_i' = min(n_i, top_k) slots), c_sim (fp64 [rows]), c_first [I]."""
+    with consensus c_order (int32 [rows]: image i's order in its first n_i' = min(n_i, top_k) slots), c_sim (fp64 [rows]), c_first [I].
+    diversity: optional {"scorer": DiversityScorer, "plan": its `plan(draws, sizes)`, "remove_bad_endings": 0 / 1}: the ranked rows and scores
+    are scored on the device in the same pass (subgc_diversity_select / _distinct / _best) -> d_int (int32 [sets, DIV_COLS + n_best]) and
+    d_f64 (fp64 [sets, n_best + 1]) in the same copy; `scorer.unpack(plan, d_int, d_f64)` makes the per-image entries."""
     import numpy as np
     dev = score.device
     rows, T = seq.shape
@@ -1495,6 +1498,10 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
     o_cons = (words + 1) & ~1                                         # the fp64 sums need an 8-byte aligned slot
     if consensus is not None:
         words = o_cons + 3 * rows + I
+    if diversity is not None:
+        d_sets, d_nb = diversity["plan"]["n_sets"], diversity["scorer"].n_best
+        o_div = (words + 1) & ~1                                      # fp64 first: 8-byte aligned
+        words = o_div + d_sets * (2 * (d_nb + 1) + DIV_COLS + d_nb)
     arena = torch.empty(max(words, 1), device=dev, dtype=torch.int32)
     o = 0
     order = arena[o:o + rows]; o += rows
@@ -1513,6 +1520,12 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
         if I and rows:
             consensus["reranker"].enqueue(seq_s.view(rows, T), seg, I, max_rows, consensus["nn"], consensus.get("top_k"),
                                           consensus.get("remove_bad_endings", 0), c_sim, c_order, c_first)
+    if diversity is not None:
+        n_f64 = 2 * d_sets * (d_nb + 1)
+        if d_sets:
+            diversity["scorer"].enqueue(seq_s.view(rows, T), score_s, seg, I, diversity["plan"], diversity.get("remove_bad_endings", 0),
+                                        arena[o_div + n_f64:o_div + n_f64 + d_sets * (DIV_COLS + d_nb)].view(d_sets, DIV_COLS + d_nb),
+                                        arena[o_div:o_div + n_f64].view(torch.float64).view(d_sets, d_nb + 1))
     if ground:
         att2 = arena[o:o + I * T1]; o += I * T1
         node = arena[o:o + I * T1]; o += I * T1
@@ -1538,6 +1551,9 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
         out["c_sim"] = host[o_cons:o_cons + 2 * rows].view(np.float64).copy()
         out["c_order"] = host[o_cons + 2 * rows:o_cons + 3 * rows].copy()
         out["c_first"] = host[o_cons + 3 * rows:o_cons + 3 * rows + I].copy()
+    if diversity is not None:
+        out["d_f64"] = host[o_div:o_div + n_f64].view(np.float64).reshape(d_sets, d_nb + 1).copy()
+        out["d_int"] = host[o_div + n_f64:o_div + n_f64 + d_sets * (DIV_COLS + d_nb)].reshape(d_sets, DIV_COLS + d_nb).copy()
     return out
 
 
@@ -1583,6 +1599,44 @@ def consensus_rank(sim, seg, I, top_k, order, first=None):
     call("subgc_consensus_rank", _ptr(sim, torch.float64), _ptr(seg, torch.int32), int(I), int(top_k), _ptr(order, torch.int32),
          _ptr(first, torch.int32), _stream())
     return order
+
+
+DIV_COLS = 8            # SUBGC_DIV_SEL: the integer columns in front of a set's selection (drawn, distinct, selected, words, unigrams, bigrams, novel, valid)
+DIV_WANT = {1: 1, 2: 2, 3: 2, 4: 4}       # metric of diversity_score.py -> SUBGC_DIV_WANT_DRAW / _WORDS / _BLEU
+
+
+def _div_tok(who, tok):
+    if tok.dtype not in (torch.int32, torch.int64) or not tok.is_contiguous() or tok.dim() != 2:
+        raise SubgcError(f"{who}: contiguous int32 / int64 token rows [rows, T], got {tok.dtype} {tuple(tok.shape)}")
+    return _ptr(tok), int(tok.dtype == torch.int64), tok.size(1)
+
+
+def diversity_select(score, seg, I, rows, set_img, set_off, draw, n_sets, n_draw, max_draw, n_best, out_i):
+    """subgc_diversity_select: per set the best n_best rows of its draw by score (later in the draw first among equal scores) into
+    out_i [n_sets, >= DIV_COLS + n_best] (diversity_score.py:63-65)."""
+    call("subgc_diversity_select", _ptr(score, torch.float32), _ptr(seg, torch.int32), int(I), int(rows), _ptr(set_img, torch.int32),
+         _ptr(set_off, torch.int32), _ptr(draw, torch.int32), int(n_sets), int(n_draw), int(max_draw), int(n_best), _ptr(out_i, torch.int32),
+         out_i.stride(0), _stream())
+    return out_i
+
+
+def diversity_distinct(tok, bad, seg, I, set_img, set_off, set_flags, draw, n_sets, n_draw, max_draw, out_i):
+    """subgc_diversity_distinct: drawn and distinct captions of every whole draw (diversity_score.py:154-160)."""
+    p_tok, t64, T = _div_tok("diversity_distinct", tok)
+    call("subgc_diversity_distinct", p_tok, t64, T, _ptr(bad, torch.uint8), 0 if bad is None else bad.numel(), _ptr(seg, torch.int32), int(I),
+         tok.size(0), _ptr(set_img, torch.int32), _ptr(set_off, torch.int32), _ptr(set_flags, torch.int32), _ptr(draw, torch.int32), int(n_sets),
+         int(n_draw), int(max_draw), _ptr(out_i, torch.int32), out_i.stride(0), _stream())
+    return out_i
+
+
+def diversity_best(tok, bad, seg, I, set_img, set_flags, n_sets, n_best, nv_off, nv_tok, nv_n, out_i, out_d):
+    """subgc_diversity_best: word / unigram / bigram / novel counts and the sentence BLEU-4 values of the rows diversity_select left in
+    out_i (diversity_score.py:67-79, 96-108, 143-145); out_d fp64 [n_sets, >= n_best + 1]."""
+    p_tok, t64, T = _div_tok("diversity_best", tok)
+    call("subgc_diversity_best", p_tok, t64, T, _ptr(bad, torch.uint8), 0 if bad is None else bad.numel(), _ptr(seg, torch.int32), int(I),
+         tok.size(0), _ptr(set_img, torch.int32), _ptr(set_flags, torch.int32), int(n_sets), int(n_best), _ptr(nv_off, torch.int32),
+         _ptr(nv_tok, torch.int32), int(nv_n), _ptr(out_i, torch.int32), out_i.stride(0), _ptr(out_d, torch.float64), out_d.stride(0), _stream())
+    return out_i, out_d
 
 
 def dropout_mask(shape, p, seed, offset, device):
