@@ -18,6 +18,8 @@ import torch  # noqa: F401  (import order matters)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_hip.h")
+# the evaluation metrics are a surface of their own (subgc_accuracy_*): same library, same contract, their own header and invoker
+METRICS_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_metrics_hip.h")
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -85,13 +87,14 @@ def lib():
                              "There is no CPU fallback for the Sub-GC hot path.")
         L = ctypes.CDLL(LIB_PATH)
         _protos = parse_header()
-        for name, (ret, args) in _protos.items():
-            try:
-                fn = getattr(L, name)
-            except AttributeError as e:
-                raise SubgcError(f"libsubgc_hip.so does not export {name} declared in subgc_hip.h") from e
-            fn.restype = ret
-            fn.argtypes = [a for a, _ in args]
+        for hdr, protos in (("subgc_hip.h", _protos), ("subgc_metrics_hip.h", parse_header(METRICS_HEADER))):
+            for name, (ret, args) in protos.items():
+                try:
+                    fn = getattr(L, name)
+                except AttributeError as e:
+                    raise SubgcError(f"libsubgc_hip.so does not export {name} declared in {hdr}") from e
+                fn.restype = ret
+                fn.argtypes = [a for a, _ in args]
         if L.subgc_version() != 1:
             raise SubgcError("libsubgc_hip.so ABI version mismatch")
         _lib = L
@@ -105,7 +108,25 @@ def call(name, *args):
     """Invoke an int-returning entry point and raise on a non-zero code."""
     fn = _FN.get(name)
     if fn is None:
-        fn = _FN[name] = getattr(lib(), name)
+        L = lib()
+        if name not in _protos:
+            raise SubgcError(f"{name} is not declared in subgc_hip.h")
+        fn = _FN[name] = getattr(L, name)
+    rc = fn(*args)
+    if rc != 0:
+        raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
+
+
+_FN_METRICS = {}  # the entry points of subgc_metrics_hip.h: a cache of their own, so that neither invoker reaches the other's header
+
+
+def call_metrics(name, *args):
+    """`call` for the entry points of subgc_metrics_hip.h."""
+    fn = _FN_METRICS.get(name)
+    if fn is None:
+        if name not in parse_header(METRICS_HEADER):
+            raise SubgcError(f"{name} is not declared in subgc_metrics_hip.h")
+        fn = _FN_METRICS[name] = getattr(lib(), name)
     rc = fn(*args)
     if rc != 0:
         raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")

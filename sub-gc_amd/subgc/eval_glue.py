@@ -62,7 +62,7 @@ def rank_subgraphs(model, seqq, subgraph_score, keep_nms_ind, sct_mode=False):
 
 
 @torch.no_grad()
-def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256, shard=False, grd_pick=None, consensus=None, diversity=None):
+def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256, shard=False, grd_pick=None, consensus=None, diversity=None, accuracy=None):
     """The testing branch of eval_split for a list of loader items: returns the `predictions` list
     (eval_utils.py:132-141): {'image_id', 'caption': [...], 'subgraph_score', 'sorted_subgraph_ind'} per image.
 
@@ -93,7 +93,14 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
     `"diversity"`: plain integer counts and fp64 values with one entry per `top_n` (`DiversityScorer.unpack`); `diversity.summarize` of
     those entries gives the numbers the script prints.  The draws come from `per_image_draws`, keyed by the image id, so `group`, the
     order of the list and `shard=True` cannot change an image's result (the script's own stream runs over the whole file;
-    `diversity.score_predictions` reproduces that one).  Works together with `consensus=`; not available in `sct` mode."""
+    `diversity.score_predictions` reproduces that one).  Works together with `consensus=`; not available in `sct` mode.
+
+    `accuracy={"scorer": AccuracyScorer, "index": {image_id: index of the image in the scorer's references}}` (default None: off) scores
+    every caption against the image's reference captions the way `test.py --only_sent_eval 1 --oracle_num N` does (sentence BLEU-1..4
+    with their material, CIDEr, ROUGE-L; the oracle picks over the first `oracle_num` captions) on the device, in the decode batch's own
+    pass and its one copy (subgc.accuracy).  Every entry gains `"accuracy"` (`AccuracyScorer.unpack`); `accuracy.summarize` of those
+    entries gives the corpus numbers, so they accumulate across batches and ranks.  The top-1 caption is caption 0, or with `consensus=`
+    the re-ranker's first choice, taken on the device.  Works together with `consensus=` and `diversity=`; not available in `sct` mode."""
     import torch.distributed as dist
     from . import parallel
     eval_kwargs = dict(eval_kwargs or {})
@@ -109,7 +116,7 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                              f"(rank {dist.get_rank()} has {len(ids)} images, the ranks hold {[len(s) for s in seen]})")
         mine, idx = parallel.shard_images(images, dist.get_rank(), world)
         local = caption_images(model, mine, [infos[i] for i in idx], ix_to_word, eval_kwargs, group, shard=False,
-                               grd_pick=None if grd_pick is None else [grd_pick[i] for i in idx], consensus=consensus, diversity=diversity)
+                               grd_pick=None if grd_pick is None else [grd_pick[i] for i in idx], consensus=consensus, diversity=diversity, accuracy=accuracy)
         return parallel.gather_by_index(local, idx, len(images))
     sct_mode = eval_kwargs.get("sct", 0) == 1
     rbe = eval_kwargs.get("remove_bad_endings", 0)
@@ -129,6 +136,14 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                              "order and are not ranked")
         from .diversity import TOP_N, per_image_draws
         d_scorer, d_top_n, d_seed = diversity["scorer"], tuple(diversity.get("top_n", TOP_N)), diversity.get("seed", 2019)
+    if accuracy is not None:
+        if sct_mode:
+            raise ValueError("caption_images: accuracy scores are not defined in sct (controllability) mode: its captions keep the input "
+                             "order and are not ranked")
+        missing = [info["id"] for info in infos if info["id"] not in accuracy["index"]]
+        if missing:
+            raise ValueError(f"caption_images: accuracy['index'] names no reference image for image ids {missing[:5]}")
+        a_scorer = accuracy["scorer"]
     was_training = model.training
     model.eval()
     predictions = []
@@ -144,6 +159,8 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                 raise ValueError("caption_images: consensus re-ranking needs a model whose sample_images exposes the decode batch (batch_out)")
             if "bounds" not in hold and diversity is not None:
                 raise ValueError("caption_images: diversity scores need a model whose sample_images exposes the decode batch (batch_out)")
+            if "bounds" not in hold and accuracy is not None:
+                raise ValueError("caption_images: accuracy scores need a model whose sample_images exposes the decode batch (batch_out)")
             if "bounds" not in hold:
                 # per image: controllability mode (input order, first half, no ranking; rare) and models whose sample_images does not
                 # expose the batch tensors
@@ -168,6 +185,8 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                         predictions[-1].update(consensus_rerank_ind=np.zeros(0, np.int64), consensus_sim=np.zeros(0, np.float64))
                     if div is not None:
                         predictions[-1]["diversity"] = d_none[j]
+                    if accuracy is not None:
+                        predictions[-1]["accuracy"] = a_scorer.unpack(np.zeros(a_scorer.arena_words(0, 1), np.int32), [0, 0])[0]
                 continue
             ground = return_att and hold.get("AL") is not None
             pick = None if grd_pick is None else grd_pick[i:i + group]
@@ -176,7 +195,10 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                                  AL=hold["AL"] if ground else None, idx=hold["idx"] if ground else None, pick=pick if ground else None,
                                  consensus=None if consensus is None else {
                                      "reranker": consensus["reranker"], "nn": [consensus["nn"][info["id"]] for info in chunk_infos],
-                                     "top_k": consensus.get("top_k"), "remove_bad_endings": rbe}, diversity=div)
+                                     "top_k": consensus.get("top_k"), "remove_bad_endings": rbe}, diversity=div,
+                                 accuracy=None if accuracy is None else {
+                                     "scorer": a_scorer, "index": [accuracy["index"][info["id"]] for info in chunk_infos], "remove_bad_endings": rbe})
+            a_entries = None if accuracy is None else a_scorer.unpack(h["a_words"], bounds)
             d_entries = None if div is None else d_scorer.unpack(d_plan, h["d_int"], h["d_f64"], d_top_n)
             ctk = None if consensus is None else consensus.get("top_k")
             for j, (info, a, b) in enumerate(zip(chunk_infos, bounds, bounds[1:])):
@@ -188,6 +210,8 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                     entry["consensus_sim"] = h["c_sim"][a:a + nc].copy()
                 if div is not None:
                     entry["diversity"] = d_entries[j]
+                if accuracy is not None:
+                    entry["accuracy"] = a_entries[j]
                 if ground:
                     w = int(h["n_words"][j])
                     sub = int(pick[j]) if pick is not None else (int(h["c_first"][j]) if consensus is not None else 0)

@@ -1471,7 +1471,7 @@ def rank_desc(score):
     return srt, order
 
 
-def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pick=None, consensus=None, diversity=None):
+def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pick=None, consensus=None, diversity=None, accuracy=None):
     """The eval loop's per-image work for a whole decode batch (misc/eval_utils.py:105-121; grounding: misc/grd_utils.py:36-47):
     one ranking launch (subgc_eval_rank_rows), one grounding launch when `AL` (the decode loop's attention buffer [T1, rows, N]) and
     `idx` (the kept sub-graphs' node lists [rows, N]) are given, and ONE device -> host copy of everything.
@@ -1484,7 +1484,12 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
     with consensus c_order (int32 [rows]: image i's order in its first n_i' = min(n_i, top_k) slots), c_sim (fp64 [rows]), c_first [I].
     diversity: optional {"scorer": DiversityScorer, "plan": its `plan(draws, sizes)`, "remove_bad_endings": 0 / 1}: the ranked rows and scores
     are scored on the device in the same pass (subgc_diversity_select / _distinct / _best) -> d_int (int32 [sets, DIV_COLS + n_best]) and
-    d_f64 (fp64 [sets, n_best + 1]) in the same copy; `scorer.unpack(plan, d_int, d_f64)` makes the per-image entries."""
+    d_f64 (fp64 [sets, n_best + 1]) in the same copy; `scorer.unpack(plan, d_int, d_f64)` makes the per-image entries.
+    accuracy: optional {"scorer": AccuracyScorer, "index": per-image reference-image indices, "remove_bad_endings": 0 / 1}: the ranked rows
+    are scored against their references on the device in the same pass (subgc_consensus_cook, subgc_accuracy_rows / _oracle of
+    subgc_metrics_hip.h); the top-1 row is the re-ranker's first choice, read from device memory, when `consensus` is given, row 0
+    otherwise -> a_words (int32: the scorer's result arena) in the same copy; `scorer.unpack(a_words, bounds)` makes the per-image entries.
+    With accuracy=None the arena, the launches and the outputs are what they are without it."""
     import numpy as np
     dev = score.device
     rows, T = seq.shape
@@ -1493,7 +1498,10 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
         raise SubgcError("eval_collect: bounds / score / keep do not cover the rows of seq")
     ground = AL is not None
     T1 = AL.size(0) if ground else 0
-    seg = upload(list(bounds) + ([0] * I if pick is None else [int(p) for p in pick]), torch.int32, dev)
+    a_index = [] if accuracy is None else accuracy["scorer"].check_index(accuracy["index"])
+    if accuracy is not None and len(a_index) != I:
+        raise SubgcError("eval_collect: accuracy needs one reference-image index per image")
+    seg = upload(list(bounds) + ([0] * I if pick is None else [int(p) for p in pick]) + a_index, torch.int32, dev)
     words = 3 * rows + rows * T + (2 * I * T1 + I if ground else 0)
     o_cons = (words + 1) & ~1                                         # the fp64 sums need an 8-byte aligned slot
     if consensus is not None:
@@ -1502,6 +1510,10 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
         d_sets, d_nb = diversity["plan"]["n_sets"], diversity["scorer"].n_best
         o_div = (words + 1) & ~1                                      # fp64 first: 8-byte aligned
         words = o_div + d_sets * (2 * (d_nb + 1) + DIV_COLS + d_nb)
+    if accuracy is not None:
+        o_acc = (words + 1) & ~1                                      # fp64 first: 8-byte aligned
+        a_words = accuracy["scorer"].arena_words(rows, I)
+        words = o_acc + a_words
     arena = torch.empty(max(words, 1), device=dev, dtype=torch.int32)
     o = 0
     order = arena[o:o + rows]; o += rows
@@ -1526,6 +1538,9 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
             diversity["scorer"].enqueue(seq_s.view(rows, T), score_s, seg, I, diversity["plan"], diversity.get("remove_bad_endings", 0),
                                         arena[o_div + n_f64:o_div + n_f64 + d_sets * (DIV_COLS + d_nb)].view(d_sets, DIV_COLS + d_nb),
                                         arena[o_div:o_div + n_f64].view(torch.float64).view(d_sets, d_nb + 1))
+    if accuracy is not None and I and rows:
+        accuracy["scorer"].enqueue(seq_s.view(rows, T), seg, I, seg[2 * I + 1:3 * I + 1], c_first, accuracy.get("remove_bad_endings", 0),
+                                   arena[o_acc:o_acc + a_words])
     if ground:
         att2 = arena[o:o + I * T1]; o += I * T1
         node = arena[o:o + I * T1]; o += I * T1
@@ -1554,6 +1569,8 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
     if diversity is not None:
         out["d_f64"] = host[o_div:o_div + n_f64].view(np.float64).reshape(d_sets, d_nb + 1).copy()
         out["d_int"] = host[o_div + n_f64:o_div + n_f64 + d_sets * (DIV_COLS + d_nb)].reshape(d_sets, DIV_COLS + d_nb).copy()
+    if accuracy is not None:
+        out["a_words"] = host[o_acc:o_acc + a_words].copy() if (I and rows) else np.zeros(a_words, np.int32)
     return out
 
 
