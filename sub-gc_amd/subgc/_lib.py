@@ -20,10 +20,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_hip.h")
 # the evaluation metrics are a surface of their own (subgc_accuracy_*): same library, same contract, their own header and invoker
 METRICS_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_metrics_hip.h")
+# the grounding scores (subgc_grounding_*): the third header, again with an invoker that knows only its own declarations
+GROUNDING_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_grounding_hip.h")
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
-    "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+    "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "uint8_t": ctypes.c_uint8,
     "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
 }
 
@@ -87,7 +89,8 @@ def lib():
                              "There is no CPU fallback for the Sub-GC hot path.")
         L = ctypes.CDLL(LIB_PATH)
         _protos = parse_header()
-        for hdr, protos in (("subgc_hip.h", _protos), ("subgc_metrics_hip.h", parse_header(METRICS_HEADER))):
+        for hdr, protos in (("subgc_hip.h", _protos), ("subgc_metrics_hip.h", parse_header(METRICS_HEADER)),
+                            ("subgc_grounding_hip.h", parse_header(GROUNDING_HEADER))):
             for name, (ret, args) in protos.items():
                 try:
                     fn = getattr(L, name)
@@ -127,6 +130,21 @@ def call_metrics(name, *args):
         if name not in parse_header(METRICS_HEADER):
             raise SubgcError(f"{name} is not declared in subgc_metrics_hip.h")
         fn = _FN_METRICS[name] = getattr(lib(), name)
+    rc = fn(*args)
+    if rc != 0:
+        raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
+
+
+_FN_GROUNDING = {}  # the entry points of subgc_grounding_hip.h
+
+
+def call_grounding(name, *args):
+    """`call` for the entry points of subgc_grounding_hip.h."""
+    fn = _FN_GROUNDING.get(name)
+    if fn is None:
+        if name not in parse_header(GROUNDING_HEADER):
+            raise SubgcError(f"{name} is not declared in subgc_grounding_hip.h")
+        fn = _FN_GROUNDING[name] = getattr(lib(), name)
     rc = fn(*args)
     if rc != 0:
         raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")

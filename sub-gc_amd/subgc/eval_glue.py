@@ -62,7 +62,8 @@ def rank_subgraphs(model, seqq, subgraph_score, keep_nms_ind, sct_mode=False):
 
 
 @torch.no_grad()
-def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256, shard=False, grd_pick=None, consensus=None, diversity=None, accuracy=None):
+def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256, shard=False, grd_pick=None, consensus=None, diversity=None, accuracy=None,
+                   grounding=None):
     """The testing branch of eval_split for a list of loader items: returns the `predictions` list
     (eval_utils.py:132-141): {'image_id', 'caption': [...], 'subgraph_score', 'sorted_subgraph_ind'} per image.
 
@@ -100,7 +101,18 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
     with their material, CIDEr, ROUGE-L; the oracle picks over the first `oracle_num` captions) on the device, in the decode batch's own
     pass and its one copy (subgc.accuracy).  Every entry gains `"accuracy"` (`AccuracyScorer.unpack`); `accuracy.summarize` of those
     entries gives the corpus numbers, so they accumulate across batches and ranks.  The top-1 caption is caption 0, or with `consensus=`
-    the re-ranker's first choice, taken on the device.  Works together with `consensus=` and `diversity=`; not available in `sct` mode."""
+    the re-ranker's first choice, taken on the device.  Works together with `consensus=` and `diversity=`; not available in `sct` mode.
+
+    `grounding={"scorer": GroundingScorer, "index": {image_id: index of the image in the scorer's references}, "boxes": {image_id: the
+    detector's boxes [N, 4]}, "img_wh": {image_id: (w, h)} or None}` (default None: off; needs `return_att`) finishes the grounding
+    experiment on the device, in the decode batch's own pass and its one copy (subgc.grounding): the sentence `"grounding"` describes --
+    `grd_pick`, else the re-ranker's first choice with `consensus=`, else caption 0 -- becomes the {'clss','idx_in_sent','bbox'} list of
+    misc/grd_utils.py:49-60 and is scored against the image's annotated captions the way misc/grounding/grounding_score.py does.  The
+    boxes are prepared as grd_utils.py:27 and the JSON round trip leave them (`boxes * max(w, h) / 592` in the array's own dtype, rounded
+    once to fp32; `img_wh` None: used as given) and go up with the batch.  Every entry gains `"grounding_score"`
+    (`GroundingScorer.unpack`: the list and the precision / recall event codes); `grounding.summarize` of those entries gives F1_all /
+    F1_loc and their parts, so they accumulate across batches and ranks.  `"grounding"` itself gains and loses nothing.  Not available in
+    `sct` mode."""
     import torch.distributed as dist
     from . import parallel
     eval_kwargs = dict(eval_kwargs or {})
@@ -116,7 +128,8 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                              f"(rank {dist.get_rank()} has {len(ids)} images, the ranks hold {[len(s) for s in seen]})")
         mine, idx = parallel.shard_images(images, dist.get_rank(), world)
         local = caption_images(model, mine, [infos[i] for i in idx], ix_to_word, eval_kwargs, group, shard=False,
-                               grd_pick=None if grd_pick is None else [grd_pick[i] for i in idx], consensus=consensus, diversity=diversity, accuracy=accuracy)
+                               grd_pick=None if grd_pick is None else [grd_pick[i] for i in idx], consensus=consensus, diversity=diversity, accuracy=accuracy,
+                               grounding=grounding)
         return parallel.gather_by_index(local, idx, len(images))
     sct_mode = eval_kwargs.get("sct", 0) == 1
     rbe = eval_kwargs.get("remove_bad_endings", 0)
@@ -144,6 +157,17 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
         if missing:
             raise ValueError(f"caption_images: accuracy['index'] names no reference image for image ids {missing[:5]}")
         a_scorer = accuracy["scorer"]
+    if grounding is not None:
+        if sct_mode:
+            raise ValueError("caption_images: grounding scores are not defined in sct (controllability) mode: its captions keep the input "
+                             "order and are not ranked")
+        if not return_att:
+            raise ValueError("caption_images: grounding scores need eval_kwargs['return_att'] = 1 (the attention arg-max of every word)")
+        missing = [info["id"] for info in infos if info["id"] not in grounding["index"] or info["id"] not in grounding["boxes"]]
+        if missing:
+            raise ValueError(f"caption_images: grounding['index'] / ['boxes'] name no reference image or no boxes for image ids {missing[:5]}")
+        from .grounding import prepare_boxes
+        g_scorer, g_wh = grounding["scorer"], grounding.get("img_wh")
     was_training = model.training
     model.eval()
     predictions = []
@@ -161,6 +185,9 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                 raise ValueError("caption_images: diversity scores need a model whose sample_images exposes the decode batch (batch_out)")
             if "bounds" not in hold and accuracy is not None:
                 raise ValueError("caption_images: accuracy scores need a model whose sample_images exposes the decode batch (batch_out)")
+            if grounding is not None and ("bounds" not in hold or hold.get("AL") is None):
+                raise ValueError("caption_images: grounding scores need a model whose sample_images exposes the decode batch and its attention "
+                                 "buffer (batch_out)")
             if "bounds" not in hold:
                 # per image: controllability mode (input order, first half, no ranking; rare) and models whose sample_images does not
                 # expose the batch tensors
@@ -187,6 +214,8 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                         predictions[-1]["diversity"] = d_none[j]
                     if accuracy is not None:
                         predictions[-1]["accuracy"] = a_scorer.unpack(np.zeros(a_scorer.arena_words(0, 1), np.int32), [0, 0])[0]
+                    if grounding is not None:
+                        predictions[-1]["grounding_score"] = g_scorer.empty_entry(g_scorer.check_index([grounding["index"][info["id"]]])[0])
                 continue
             ground = return_att and hold.get("AL") is not None
             pick = None if grd_pick is None else grd_pick[i:i + group]
@@ -197,7 +226,12 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                                      "reranker": consensus["reranker"], "nn": [consensus["nn"][info["id"]] for info in chunk_infos],
                                      "top_k": consensus.get("top_k"), "remove_bad_endings": rbe}, diversity=div,
                                  accuracy=None if accuracy is None else {
-                                     "scorer": a_scorer, "index": [accuracy["index"][info["id"]] for info in chunk_infos], "remove_bad_endings": rbe})
+                                     "scorer": a_scorer, "index": [accuracy["index"][info["id"]] for info in chunk_infos], "remove_bad_endings": rbe},
+                                 grounding=None if grounding is None else {
+                                     "scorer": g_scorer, "index": [grounding["index"][info["id"]] for info in chunk_infos], "remove_bad_endings": rbe,
+                                     "boxes": [prepare_boxes(grounding["boxes"][info["id"]], None if g_wh is None else g_wh[info["id"]])
+                                               for info in chunk_infos]})
+            g_entries = None if grounding is None else g_scorer.unpack(h["g_words"], h["g_plan"])
             a_entries = None if accuracy is None else a_scorer.unpack(h["a_words"], bounds)
             d_entries = None if div is None else d_scorer.unpack(d_plan, h["d_int"], h["d_f64"], d_top_n)
             ctk = None if consensus is None else consensus.get("top_k")
@@ -217,6 +251,8 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                     sub = int(pick[j]) if pick is not None else (int(h["c_first"][j]) if consensus is not None else 0)
                     entry["grounding"] = {"subg_index": sub, "sort_ind": h["order"][a:b],
                                           "att2_ind": h["att2"][j, :w].astype(np.int64), "node_ind": h["node"][j, :w].astype(np.int64)}
+                    if grounding is not None:
+                        entry["grounding_score"] = g_entries[j]
                 predictions.append(entry)
     finally:
         model.train(was_training)

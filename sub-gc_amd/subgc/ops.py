@@ -1471,7 +1471,8 @@ def rank_desc(score):
     return srt, order
 
 
-def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pick=None, consensus=None, diversity=None, accuracy=None):
+def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pick=None, consensus=None, diversity=None, accuracy=None,
+                 grounding=None):
     """The eval loop's per-image work for a whole decode batch (misc/eval_utils.py:105-121; grounding: misc/grd_utils.py:36-47):
     one ranking launch (subgc_eval_rank_rows), one grounding launch when `AL` (the decode loop's attention buffer [T1, rows, N]) and
     `idx` (the kept sub-graphs' node lists [rows, N]) are given, and ONE device -> host copy of everything.
@@ -1489,7 +1490,12 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
     are scored against their references on the device in the same pass (subgc_consensus_cook, subgc_accuracy_rows / _oracle of
     subgc_metrics_hip.h); the top-1 row is the re-ranker's first choice, read from device memory, when `consensus` is given, row 0
     otherwise -> a_words (int32: the scorer's result arena) in the same copy; `scorer.unpack(a_words, bounds)` makes the per-image entries.
-    With accuracy=None the arena, the launches and the outputs are what they are without it."""
+    With accuracy=None the arena, the launches and the outputs are what they are without it.
+    grounding: optional {"scorer": GroundingScorer, "index": per-image reference-image indices, "boxes": per image its fp32 boxes [N_i, 4]
+    in image scale (`grounding.prepare_boxes`), "remove_bad_endings": 0 / 1}; needs AL / idx.  Behind the grounding arg-max the chosen
+    captions become {'clss','idx_in_sent','bbox'} lists and precision / recall event codes on the device (subgc_grounding_material /
+    _score of subgc_grounding_hip.h); the boxes go up with the batch -> g_words (int32: the scorer's result arena) in the same copy and
+    g_plan; `scorer.unpack(g_words, g_plan)` makes the per-image entries.  With grounding=None nothing changes."""
     import numpy as np
     dev = score.device
     rows, T = seq.shape
@@ -1501,7 +1507,18 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
     a_index = [] if accuracy is None else accuracy["scorer"].check_index(accuracy["index"])
     if accuracy is not None and len(a_index) != I:
         raise SubgcError("eval_collect: accuracy needs one reference-image index per image")
-    seg = upload(list(bounds) + ([0] * I if pick is None else [int(p) for p in pick]) + a_index, torch.int32, dev)
+    g_tab = []
+    if grounding is not None:
+        if not ground:
+            raise SubgcError("eval_collect: grounding scores need the decode loop's attention buffer (AL / idx)")
+        g_sc = grounding["scorer"]
+        g_plan = g_sc.plan(grounding["index"])
+        if g_plan["I"] != I or len(grounding["boxes"]) != I:
+            raise SubgcError("eval_collect: grounding needs one reference-image index and one box array per image")
+        g_box = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 4) for b in grounding["boxes"]]
+        g_tab = g_plan["table"].tolist() + np.concatenate([[0], np.cumsum([len(b) for b in g_box])]).astype(np.int64).tolist()
+        g_nbox = sum(len(b) for b in g_box)
+    seg = upload(list(bounds) + ([0] * I if pick is None else [int(p) for p in pick]) + a_index + g_tab, torch.int32, dev)
     words = 3 * rows + rows * T + (2 * I * T1 + I if ground else 0)
     o_cons = (words + 1) & ~1                                         # the fp64 sums need an 8-byte aligned slot
     if consensus is not None:
@@ -1514,6 +1531,10 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
         o_acc = (words + 1) & ~1                                      # fp64 first: 8-byte aligned
         a_words = accuracy["scorer"].arena_words(rows, I)
         words = o_acc + a_words
+    if grounding is not None:
+        o_grd = words
+        g_words = g_sc.arena_words(g_plan)
+        words = o_grd + g_words
     arena = torch.empty(max(words, 1), device=dev, dtype=torch.int32)
     o = 0
     order = arena[o:o + rows]; o += rows
@@ -1548,10 +1569,14 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
         if AL.stride(2) != 1 or idx.stride(1) != 1:
             raise SubgcError("eval_collect: AL / idx need unit inner strides")
         if I:
+            g_pick = seg[I + 1:2 * I + 1] if pick is not None else (c_first if (c_first is not None and rows) else None)
             call("subgc_grounding_argmax", _ptr(AL, torch.float32), AL.stride(0), AL.stride(1), AL.size(2), T1, _ptr(seq.contiguous(), torch.int64), T,
-                 _ptr(idx, torch.int64), idx.stride(0), _ptr(seg), _ptr(order) if (rows and not identity) else None,
-                 _ptr(seg[I + 1:]) if pick is not None else (_ptr(c_first) if (c_first is not None and rows) else None), I, _ptr(att2), _ptr(node),
-                 _ptr(nw), _stream())
+                 _ptr(idx, torch.int64), idx.stride(0), _ptr(seg), _ptr(order) if (rows and not identity) else None, _ptr(g_pick), I, _ptr(att2),
+                 _ptr(node), _ptr(nw), _stream())
+            if grounding is not None:
+                g_dbox = upload(np.concatenate(g_box).ravel() if g_nbox else np.zeros(4, np.float32), torch.float32, dev)
+                g_sc.enqueue(seq_s.view(rows, T), seg, g_pick, I, node, T1, nw, seg[2 * I + 1 + len(a_index):], g_dbox, g_nbox,
+                             grounding.get("remove_bad_endings", 0), arena[o_grd:o_grd + g_words], g_plan)
     host = arena.cpu().numpy()                                        # the one copy (synchronises the stream)
     o = 0
     out = {"order": host[o:o + rows].astype(np.int64)}; o += rows
@@ -1571,6 +1596,8 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
         out["d_int"] = host[o_div + n_f64:o_div + n_f64 + d_sets * (DIV_COLS + d_nb)].reshape(d_sets, DIV_COLS + d_nb).copy()
     if accuracy is not None:
         out["a_words"] = host[o_acc:o_acc + a_words].copy() if (I and rows) else np.zeros(a_words, np.int32)
+    if grounding is not None:
+        out["g_words"], out["g_plan"] = host[o_grd:o_grd + g_words].copy(), g_plan
     return out
 
 
