@@ -22,6 +22,8 @@ HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc
 METRICS_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_metrics_hip.h")
 # the grounding scores (subgc_grounding_*): the third header, again with an invoker that knows only its own declarations
 GROUNDING_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_grounding_hip.h")
+# the set-controllability score (subgc_control_*): the fourth header, same arrangement
+CONTROLLABILITY_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_controllability_hip.h")
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -90,7 +92,8 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         _protos = parse_header()
         for hdr, protos in (("subgc_hip.h", _protos), ("subgc_metrics_hip.h", parse_header(METRICS_HEADER)),
-                            ("subgc_grounding_hip.h", parse_header(GROUNDING_HEADER))):
+                            ("subgc_grounding_hip.h", parse_header(GROUNDING_HEADER)),
+                            ("subgc_controllability_hip.h", parse_header(CONTROLLABILITY_HEADER))):
             for name, (ret, args) in protos.items():
                 try:
                     fn = getattr(L, name)
@@ -145,6 +148,21 @@ def call_grounding(name, *args):
         if name not in parse_header(GROUNDING_HEADER):
             raise SubgcError(f"{name} is not declared in subgc_grounding_hip.h")
         fn = _FN_GROUNDING[name] = getattr(lib(), name)
+    rc = fn(*args)
+    if rc != 0:
+        raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
+
+
+_FN_CONTROLLABILITY = {}  # the entry points of subgc_controllability_hip.h
+
+
+def call_controllability(name, *args):
+    """`call` for the entry points of subgc_controllability_hip.h."""
+    fn = _FN_CONTROLLABILITY.get(name)
+    if fn is None:
+        if name not in parse_header(CONTROLLABILITY_HEADER):
+            raise SubgcError(f"{name} is not declared in subgc_controllability_hip.h")
+        fn = _FN_CONTROLLABILITY[name] = getattr(lib(), name)
     rc = fn(*args)
     if rc != 0:
         raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")

@@ -63,7 +63,7 @@ def rank_subgraphs(model, seqq, subgraph_score, keep_nms_ind, sct_mode=False):
 
 @torch.no_grad()
 def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256, shard=False, grd_pick=None, consensus=None, diversity=None, accuracy=None,
-                   grounding=None):
+                   grounding=None, controllability=None):
     """The testing branch of eval_split for a list of loader items: returns the `predictions` list
     (eval_utils.py:132-141): {'image_id', 'caption': [...], 'subgraph_score', 'sorted_subgraph_ind'} per image.
 
@@ -112,7 +112,17 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
     once to fp32; `img_wh` None: used as given) and go up with the batch.  Every entry gains `"grounding_score"`
     (`GroundingScorer.unpack`: the list and the precision / recall event codes); `grounding.summarize` of those entries gives F1_all /
     F1_loc and their parts, so they accumulate across batches and ranks.  `"grounding"` itself gains and loses nothing.  Not available in
-    `sct` mode."""
+    `sct` mode.
+
+    `controllability={"scorer": ControlScorer, "index": {image_id: index of the image's first group in the scorer's references}}` (default
+    None: off; available ONLY in `sct` mode) scores the set-controllability run the way misc/controllability/controllability_score.py
+    does (subgc.controllability): an image's kept rows (the first half, in input order) are the generated captions of its consecutive
+    groups, index .. index + rows - 1.  The decode stays per image; the kept rows of a chunk are scored together in one
+    `ControlScorer.score` call -- the Noun IoU launch, the accuracy launches, one host copy -- and every entry gains `"controllability"`: the
+    per-row entries of its rows (Noun IoU with its pairs and assignments, BLEU material, CIDEr, ROUGE-L against the row's group);
+    `controllability.summarize` of those entries, flattened in `order_list` order, gives the script's numbers.  `index` holds the first
+    group of EVERY image of the references: an image's number of groups is the distance to the next first group (the last image's: to
+    the number of groups), and an image whose kept rows differ from it in number is an error that names the image id."""
     import torch.distributed as dist
     from . import parallel
     eval_kwargs = dict(eval_kwargs or {})
@@ -129,7 +139,7 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
         mine, idx = parallel.shard_images(images, dist.get_rank(), world)
         local = caption_images(model, mine, [infos[i] for i in idx], ix_to_word, eval_kwargs, group, shard=False,
                                grd_pick=None if grd_pick is None else [grd_pick[i] for i in idx], consensus=consensus, diversity=diversity, accuracy=accuracy,
-                               grounding=grounding)
+                               grounding=grounding, controllability=controllability)
         return parallel.gather_by_index(local, idx, len(images))
     sct_mode = eval_kwargs.get("sct", 0) == 1
     rbe = eval_kwargs.get("remove_bad_endings", 0)
@@ -168,6 +178,16 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
             raise ValueError(f"caption_images: grounding['index'] / ['boxes'] name no reference image or no boxes for image ids {missing[:5]}")
         from .grounding import prepare_boxes
         g_scorer, g_wh = grounding["scorer"], grounding.get("img_wh")
+    if controllability is not None:
+        if not sct_mode:
+            raise ValueError("caption_images: controllability scores are defined only in sct (controllability) mode (eval_kwargs['sct'] = 1): "
+                             "they need one caption per input region set, in input order")
+        missing = [info["id"] for info in infos if info["id"] not in controllability["index"]]
+        if missing:
+            raise ValueError(f"caption_images: controllability['index'] names no first group for image ids {missing[:5]}")
+        c_scorer = controllability["scorer"]
+        firsts = sorted(set(int(v) for v in controllability["index"].values())) + [c_scorer.refs.n_groups]
+        c_count = {a: b - a for a, b in zip(firsts, firsts[1:])}
     was_training = model.training
     model.eval()
     predictions = []
@@ -191,10 +211,14 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
             if "bounds" not in hold:
                 # per image: controllability mode (input order, first half, no ranking; rare) and models whose sample_images does not
                 # expose the batch tensors
+                kept = []
                 for info, r in zip(chunk_infos, results):
                     seq, score, sorted_ind, _ = rank_subgraphs(model, r[0], r[2], r[3], sct_mode)
                     predictions.append({"image_id": info["id"], "caption": decode_sequence(ix_to_word, seq, rbe),
                                         "subgraph_score": score.cpu().numpy(), "sorted_subgraph_ind": sorted_ind.cpu().numpy()})
+                    kept.append(seq)
+                if controllability is not None:
+                    _score_controllability(c_scorer, controllability["index"], c_count, chunk_infos, kept, predictions[len(predictions) - len(kept):], rbe)
                 continue
             bounds = hold["bounds"]
             div = None
@@ -257,6 +281,25 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
     finally:
         model.train(was_training)
     return predictions
+
+
+def _score_controllability(scorer, index, count, infos, kept, entries, rbe):
+    """The kept rows of a chunk of `sct` images (one [rows_i, T_i] tensor each) -> one `ControlScorer.score` call; entry i gains
+    `"controllability"`: the per-row entries of its rows."""
+    groups = []
+    for info, seq in zip(infos, kept):
+        first = int(index[info["id"]])
+        if seq.size(0) != count.get(first, -1):
+            raise ValueError(f"caption_images: image {info['id']!r} has {seq.size(0)} kept rows and {count.get(first, 0)} ground-truth groups "
+                             f"(first group {first}); controllability scores need one caption per region set")
+        groups += list(range(first, first + seq.size(0)))
+    T = max(int(seq.size(1)) for seq in kept)
+    rows = torch.cat([seq if seq.size(1) == T else torch.nn.functional.pad(seq, (0, T - seq.size(1))) for seq in kept])
+    scored = scorer.score(rows, groups, remove_bad_endings=rbe) if groups else []
+    a = 0
+    for e, seq in zip(entries, kept):
+        e["controllability"] = scored[a:a + seq.size(0)]
+        a += seq.size(0)
 
 
 def _sample_batch(model, chunk, eval_kwargs, hold):
