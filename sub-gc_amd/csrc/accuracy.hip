@@ -2,7 +2,8 @@
 // (pycocoevalcap/bleu/bleu_scorer.py:26-93,208-256), CIDEr (pycocoevalcap/cider/cider_scorer.py:95-184) and ROUGE-L
 // (pycocoevalcap/rouge/rouge.py:15-77) against the reference captions of the row's image, then per image the oracle picks over its
 // first oracle_num rows and the top-1 row (misc/sentence_utils.py:28-53,108-125).  Two kernels: one workgroup per row, one per image.
-// Words are 16-bit ids and n-grams 64-bit keys as in consensus.hip, whose cook launch prepares the tf-idf lists of both sides; counts
+// Words are 16-bit ids and n-grams 64-bit keys by caption.h, which also holds the caption rule of a token row; consensus.hip's cook
+// launch prepares the tf-idf lists of both sides; counts
 // are integers (LDS integer adds: order-free), the arithmetic is fp64 in the reference's own order, summed by one thread, with FMA
 // contraction off for the whole file: equal inputs give equal bits, and ROUGE-L's and CIDEr's expressions round as Python's do.
 #include "common.h"
@@ -11,6 +12,8 @@
 
 #pragma clang fp contract(off)
 
+#include "caption.h"      // after the pragma: its functions are compiled without contraction here
+
 namespace {
 
 constexpr int kRowWords = 64;                           // words of a candidate row (the decode's T): one wavefront
@@ -18,33 +21,11 @@ constexpr int kRefWords = SUBGC_ACC_MAX_REF_WORDS;      // words of a reference 
 constexpr int kMaxRefs = SUBGC_ACC_MAX_REFS;            // reference captions of an image
 constexpr int kRowKeys = 4 * kRowWords;                 // n-grams of a row, all orders
 
-__device__ __forceinline__ int key_order(uint64_t k) {                     // 0 .. 3 for a 1- .. 4-gram: the last non-zero 16-bit lane
-    return (k & 0xffffull) ? 3 : ((k & 0xffff0000ull) ? 2 : ((k & 0xffff00000000ull) ? 1 : 0));
-}
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// One WAVE (all 64 lanes) reads row r of tok [rows, T], T <= 64: -> the caption's length (ids before the first id <= 0, minus trailing
-// words w with bad[w] != 0 unless every word is one: misc/utils.py:74-80, exactly cook_kernel's rule); w = the lane's word
-__device__ __forceinline__ int load_row(const void* __restrict__ tok, int tok64, int T, int64_t r, const uint8_t* __restrict__ bad, int bad_n,
-                                        int lane, uint32_t& w) {
-    const int64_t v = lane < T ? (tok64 ? static_cast<const int64_t*>(tok)[r * T + lane] : (int64_t)static_cast<const int32_t*>(tok)[r * T + lane]) : 0;
-    const unsigned long long stop = ~__ballot(v > 0);
-    int L = stop ? __ffsll((long long)stop) - 1 : 64;
-    if (L > T) L = T;
-    if (bad) {
-        const unsigned long long good = __ballot(lane < L && !(v > 0 && v < bad_n && bad[(v > 0 && v < bad_n) ? v : 0]));
-        if (good) L = 64 - __clzll((long long)good);
-    }
-    w = (uint32_t)v & 0xffffu;
-    return L;
-}
-
 // One workgroup (4 waves) per candidate row.
 //   BLEU: the row's <= 250 n-gram keys in LDS; the first occurrence of a key counts its repeats, finds the image's largest reference
 //     count by binary search in the image's sorted table and adds min(count, that) to its order (cook_test, bleu_scorer.py:88-91).
-//   CIDEr: thread s < R walks reference s's cooked list once while a cursor advances through the row's (in LDS): a matching key adds
-//     min(w_hyp, w_ref) * w_ref to its order's sum in ascending key order (sim, cider_scorer.py:139-147), then the norm division and the
-//     length factor (:149-154); the R results wait in LDS for the one thread that adds them in reference order.
+//   CIDEr: thread s < R scores reference s against the row's cooked list (in LDS) by caption.h's cider_walk and cider_finish (sim,
+//     cider_scorer.py:139-154); the R results wait in LDS for the one thread that adds them in reference order.
 //   ROUGE-L: lane j of a wave holds word j of the row; a reference goes to a wave, each of its words w is one match mask
 //     __ballot(word_j == w) and one step U = V & M, V = (V + U) | (V - U) of the bit-vector LCS on a 64-bit word; the LCS is the number of
 //     zero bits among the row's low bits (my_lcs, rouge.py:15-37, without its table).
@@ -83,9 +64,9 @@ __global__ __launch_bounds__(256) void rows_kernel(const void* __restrict__ tok,
     const int cstride = 4 * T;
     const int na = clampi(ccnt[r], 0, cstride < kRowKeys ? cstride : kRowKeys);
     if (wave == 0) {
-        uint32_t w;
-        const int L = load_row(tok, tok64, T, r, bad, bad_n, lane, w);
-        tk[lane] = lane < L ? w : 0u;
+        int64_t v;
+        const int L = load_row(tok, tok64, T, r, bad, bad_n, lane, v);
+        tk[lane] = lane < L ? (uint32_t)v & 0xffffu : 0u;
         if (lane == 0) L_sh = L;
     }
     if (t < 4) correct[t] = 0;
@@ -99,20 +80,14 @@ __global__ __launch_bounds__(256) void rows_kernel(const void* __restrict__ tok,
     for (int o = 0; o < 4; ++o) {
         const int c = L - o;
         if (c <= 0) break;
-        if (t < c) {
-            uint64_t key = (uint64_t)tk[t] << 48;
-            if (o >= 1) key |= (uint64_t)tk[t + 1] << 32;
-            if (o >= 2) key |= (uint64_t)tk[t + 2] << 16;
-            if (o >= 3) key |= (uint64_t)tk[t + 3];
-            gk[nk + t] = key;
-        }
+        if (t < c) gk[nk + t] = ngram_key(tk, t, o);
         nk += c;
     }
     __syncthreads();
     for (int g = t; g < nk; g += 256) {
         const uint64_t key = gk[g];
-        int c = 0, before = 0;
-        for (int q = 0; q < nk; ++q) {
+        int c = 0, before = 0;                                              // caption.h's count_key, kept inline: through the function this
+        for (int q = 0; q < nk; ++q) {                                      // kernel measured 0.8 us of 69 slower (profiles/r14)
             const bool same = gk[q] == key;
             c += same;
             before += same && q < g;
@@ -133,39 +108,14 @@ __global__ __launch_bounds__(256) void rows_kernel(const void* __restrict__ tok,
         const int Lr = w1 - w0 < kRefWords ? w1 - w0 : kRefWords;
         const int64_t base = 4 * (int64_t)w0;
         const int nb = clampi(rcnt[s], 0, 4 * Lr);
-        double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
-        int ia = 0;
-        uint64_t ck = na > 0 ? hk[0] : ~0ull;
-#pragma unroll 4
-        for (int ib = 0; ib < nb; ++ib) {
-            const uint64_t key = rkeys[base + ib];
-            const double w = rw[base + ib];
-            while (ck < key) {
-                ++ia;
-                ck = ia < na ? hk[ia] : ~0ull;
-            }
-            if (ck == key && ia < na) {
-                const double term = fmin(hw[ia], w) * w;
-                const int o = key_order(key);
-                v0 += o == 0 ? term : 0.0;
-                v1 += o == 1 ? term : 0.0;
-                v2 += o == 2 ? term : 0.0;
-                v3 += o == 3 ? term : 0.0;
-            }
-        }
-        const double h0 = cnorm[(int64_t)r * 4], h1 = cnorm[(int64_t)r * 4 + 1], h2 = cnorm[(int64_t)r * 4 + 2], h3 = cnorm[(int64_t)r * 4 + 3];
-        const double r0 = rnorm[(int64_t)s * 4], r1 = rnorm[(int64_t)s * 4 + 1], r2 = rnorm[(int64_t)s * 4 + 2], r3 = rnorm[(int64_t)s * 4 + 3];
+        double v[4];
+        cider_walk(hk, hw, na, rkeys, rw, base, nb, v);
+        const double hn[4] = {cnorm[(int64_t)r * 4], cnorm[(int64_t)r * 4 + 1], cnorm[(int64_t)r * 4 + 2], cnorm[(int64_t)r * 4 + 3]};
+        const double rn[4] = {rnorm[(int64_t)s * 4], rnorm[(int64_t)s * 4 + 1], rnorm[(int64_t)s * 4 + 2], rnorm[(int64_t)s * 4 + 3]};
         int d = clen[r] - rlen[s];
         d = d < 0 ? -d : d;
-        const double g = gauss[clampi(d, 0, n_gauss - 1)];
-        if (h0 != 0.0 && r0 != 0.0) v0 /= h0 * r0;
-        if (h1 != 0.0 && r1 != 0.0) v1 /= h1 * r1;
-        if (h2 != 0.0 && r2 != 0.0) v2 /= h2 * r2;
-        if (h3 != 0.0 && r3 != 0.0) v3 /= h3 * r3;
-        cval[t * 4] = v0 * g;
-        cval[t * 4 + 1] = v1 * g;
-        cval[t * 4 + 2] = v2 * g;
-        cval[t * 4 + 3] = v3 * g;
+        cider_finish(v, hn, rn, gauss[clampi(d, 0, n_gauss - 1)]);
+        for (int k = 0; k < 4; ++k) cval[t * 4 + k] = v[k];
         wl_sh[t] = Lr;
     }
     // ROUGE-L: `split(" ")` makes an empty caption ONE word, the empty word (id 0: never a real word), on both sides
@@ -203,13 +153,8 @@ __global__ __launch_bounds__(256) void rows_kernel(const void* __restrict__ tok,
     int32_t* oi = out_i + (int64_t)r * ld_i;
     double* od = out_d + (int64_t)r * ld_d;
     const double small = 1e-9, tiny = 1e-15;
-    // BLEU (bleu_scorer.py:76-77 `min((abs(l - testlen), l) for l in reflen)[1]`: the closest length, the shorter on a tie; :242-252)
-    const int testlen = L;
-    int best_d = 1 << 30, reflen = 0;
-    for (int s = 0; s < R; ++s) {
-        const int l = wl_sh[s], d = l > testlen ? l - testlen : testlen - l;
-        if (d < best_d || (d == best_d && l < reflen)) { best_d = d; reflen = l; }
-    }
+    // BLEU (bleu_scorer.py:76-77, the closest reference length; :242-252)
+    const int testlen = L, reflen = closest_len(wl_sh, R, -1, testlen);
     oi[SUBGC_ACC_TESTLEN] = testlen;
     oi[SUBGC_ACC_REFLEN] = reflen;
     double prod = 1.0, bl[4];
@@ -303,41 +248,6 @@ __global__ __launch_bounds__(256) void oracle_kernel(const int32_t* __restrict__
     }
 }
 
-// debug bounds mode: 0 <= seg[i] <= seg[i+1] <= rows for every image; out[0] = violations, out[1] = the first image
-__global__ __launch_bounds__(256) void check_seg_kernel(const int32_t* __restrict__ seg, int I, int rows, unsigned long long* __restrict__ out) {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < I; i += gridDim.x * 256) {
-        const int a = seg[i], b = seg[i + 1];
-        if (a < 0 || b < a || b > rows) {
-            atomicAdd(out, 1ull);
-            atomicMin(out + 1, (unsigned long long)i);
-        }
-    }
-}
-
-int check_seg(const char* who, const int32_t* seg, int I, int rows, hipStream_t s) {
-    if (!subgc::debug_bounds()) return SUBGC_OK;
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return SUBGC_OK; }
-    if (st != hipStreamCaptureStatusNone) return SUBGC_OK;
-    unsigned long long* out = nullptr;
-    unsigned long long res[2] = {0ull, ~0ull};
-    if (hipMalloc(&out, sizeof(res)) != hipSuccess) { subgc::set_error("%s: debug check cannot allocate its result word", who); return SUBGC_ELAUNCH; }
-    bool ok = hipMemcpyAsync(out, res, sizeof(res), hipMemcpyHostToDevice, s) == hipSuccess;
-    if (ok) {
-        hipLaunchKernelGGL(check_seg_kernel, dim3((int)subgc::cdiv(I, 256) < 64 ? (int)subgc::cdiv(I, 256) : 64), dim3(256), 0, s, seg, I, rows, out);
-        ok = hipGetLastError() == hipSuccess;
-    }
-    ok = ok && hipMemcpyAsync(res, out, sizeof(res), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    (void)hipFree(out);
-    if (!ok) { subgc::set_error("%s: debug check failed to run: %s", who, hipGetErrorString(hipGetLastError())); return SUBGC_ELAUNCH; }
-    if (res[0] == 0) return SUBGC_OK;
-    int32_t ab[2] = {0, 0};
-    (void)hipMemcpy(ab, seg + res[1], sizeof(ab), hipMemcpyDeviceToHost);
-    subgc::set_error("%s: seg (row boundaries of the images) is not monotone inside [0, %d] (%llu images; first at image %llu: %d .. %d) "
-                     "[debug bounds mode]", who, rows, res[0], res[1], ab[0], ab[1]);
-    return SUBGC_EINVAL;
-}
-
 }  // namespace
 
 SUBGC_API int subgc_accuracy_rows(const void* tok, int tok64, int T, const uint8_t* bad, int bad_n, int rows, const int32_t* seg, int I,
@@ -359,7 +269,7 @@ SUBGC_API int subgc_accuracy_rows(const void* tok, int tok64, int T, const uint8
                       out_i && out_d && (n_words == 0 || (rtok && rkeys && rw)) && (n_bkeys == 0 || (bkeys && bmax)),
                   "accuracy_rows: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = check_seg("accuracy_rows", seg, I, rows, s)) return rc;
+    SUBGC_DEBUG_MONO("accuracy_rows", "seg (row boundaries of the images)", "image", seg, I, rows, s);
     SUBGC_DEBUG_RANGE(img_ref, 4, 1, I, I, 0, (int64_t)n_ref - 1, -1, "accuracy_rows: img_ref (reference image of every batch image)", s);
     SUBGC_DEBUG_RANGE(cap_off, 4, 1, (int64_t)n_ref + 1, (int64_t)n_ref + 1, 0, n_caps, -1, "accuracy_rows: cap_off (CSR caption offsets)", s);
     SUBGC_DEBUG_RANGE(rwoff, 4, 1, (int64_t)n_caps + 1, (int64_t)n_caps + 1, 0, n_words, -1, "accuracy_rows: rwoff (CSR word offsets)", s);
@@ -380,7 +290,7 @@ SUBGC_API int subgc_accuracy_oracle(const int32_t* row_i, int ld_i, const double
     if (I == 0) return SUBGC_OK;
     SUBGC_REQUIRE(seg && img_i && img_d && (rows == 0 || (row_i && row_d)), "accuracy_oracle: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = check_seg("accuracy_oracle", seg, I, rows, s)) return rc;
+    SUBGC_DEBUG_MONO("accuracy_oracle", "seg (row boundaries of the images)", "image", seg, I, rows, s);
     hipLaunchKernelGGL(oracle_kernel, dim3(I), dim3(256), 0, s, row_i, ld_i, row_d, ld_d, rows, seg, I, oracle_num, first, img_i, ld_ii, img_d, ld_id);
     return subgc::check_launch("subgc_accuracy_oracle");
 }

@@ -58,6 +58,24 @@ int debug_check_range(const void* x, int elem, int64_t rows, int64_t cols, int64
                       hipStream_t s);
 // gpn.py:117-118: a sub-graph's node list holds the dummy node (N - 1) exactly where its attention mask is zero
 int debug_check_mask_agrees(const int64_t* obj_ind, const float* mask, int64_t n, int64_t dummy, const char* what, hipStream_t s);
+// an offset table: 0 <= off[i] <= off[i + 1] <= top for every i < n; `what` names the table and `noun` a position of it in the error text
+int debug_check_mono(const char* who, const char* what, const char* noun, const int32_t* off, int64_t n, int64_t top, hipStream_t s);
+// the plumbing of such a check, for the one a file keeps to itself: a check is skipped while `s` is being captured (it synchronises) ...
+bool capturing(hipStream_t s);
+// ... and otherwise runs `launch(out)` on s and waits: res = (violations, the smallest value the kernel atomicMin'ed into out[1]).
+// -> SUBGC_OK or SUBGC_ELAUNCH with the error text set
+template <typename F>
+int run_check(hipStream_t s, F&& launch, unsigned long long (&res)[2], const char* what) {
+    unsigned long long* out = nullptr;
+    if (hipMalloc(&out, 2 * sizeof(unsigned long long)) != hipSuccess) { set_error("%s: debug check cannot allocate its result word", what); return SUBGC_ELAUNCH; }
+    const unsigned long long init[2] = {0ull, ~0ull};
+    bool ok = hipMemcpyAsync(out, init, sizeof(init), hipMemcpyHostToDevice, s) == hipSuccess;
+    if (ok) { launch(out); ok = hipGetLastError() == hipSuccess; }
+    ok = ok && hipMemcpyAsync(res, out, sizeof(res), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+    (void)hipFree(out);
+    if (!ok) { set_error("%s: debug check failed to run: %s", what, hipGetErrorString(hipGetLastError())); return SUBGC_ELAUNCH; }
+    return SUBGC_OK;
+}
 // bytes an LSTM cell forward launch over n = rows x R hidden units moves: `parts` pre-activation planes + the additive gate terms (4 floats
 // per unit each), c_prev, c, the h destinations (fp32 or bf16) and the saved gates -- against the 12 floats per unit of the algorithmic count
 inline double lstm_fwd_moved_bytes(int64_t n, int parts, bool g1, bool g2, bool c_prev, bool h2, bool hdrop, bool gates, int h_bf16) {
@@ -138,6 +156,12 @@ __device__ __forceinline__ float4 subgc_load_q(const float* __restrict__ ah, con
     do {                                                                                                                        \
         if (subgc::debug_bounds())                                                                                             \
             if (int rc_ = subgc::debug_check_range(x, elem, rows, cols, ld, lo, hi, also_ok, what, (hipStream_t)(s))) return rc_; \
+    } while (0)
+
+#define SUBGC_DEBUG_MONO(who, what, noun, off, n, top, s)                                                                      \
+    do {                                                                                                                        \
+        if (subgc::debug_bounds())                                                                                             \
+            if (int rc_ = subgc::debug_check_mono(who, what, noun, off, n, top, (hipStream_t)(s))) return rc_;                  \
     } while (0)
 
 #define SUBGC_REQUIRE(cond, ...)          \

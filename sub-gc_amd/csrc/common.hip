@@ -66,25 +66,22 @@ __global__ __launch_bounds__(256) void mask_agree_kernel(const int64_t* __restri
             atomicMin(out + 1, (unsigned long long)i);
         }
 }
+__global__ __launch_bounds__(256) void mono_check_kernel(const int32_t* __restrict__ off, int64_t n, long long top, unsigned long long* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const long long a = off[i], b = off[i + 1];
+        if (a < 0 || b < a || b > top) {
+            atomicAdd(out, 1ull);
+            atomicMin(out + 1, (unsigned long long)i);
+        }
+    }
+}
+}  // namespace
+
 bool capturing(hipStream_t s) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
     return st != hipStreamCaptureStatusNone;
 }
-// runs `launch(out)` on s, waits, -> (violations, first position); < 0: runtime error
-template <typename F>
-int run_check(hipStream_t s, F&& launch, unsigned long long (&res)[2], const char* what) {
-    unsigned long long* out = nullptr;
-    if (hipMalloc(&out, 2 * sizeof(unsigned long long)) != hipSuccess) { set_error("%s: debug check cannot allocate its result word", what); return SUBGC_ELAUNCH; }
-    const unsigned long long init[2] = {0ull, ~0ull};
-    bool ok = hipMemcpyAsync(out, init, sizeof(init), hipMemcpyHostToDevice, s) == hipSuccess;
-    if (ok) { launch(out); ok = hipGetLastError() == hipSuccess; }
-    ok = ok && hipMemcpyAsync(res, out, sizeof(res), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    (void)hipFree(out);
-    if (!ok) { set_error("%s: debug check failed to run: %s", what, hipGetErrorString(hipGetLastError())); return SUBGC_ELAUNCH; }
-    return SUBGC_OK;
-}
-}  // namespace
 
 bool debug_bounds() { return g_debug_bounds.load(std::memory_order_relaxed) != 0; }
 
@@ -111,6 +108,20 @@ int debug_check_range(const void* x, int elem, int64_t rows, int64_t cols, int64
     else { int32_t t = 0; (void)hipMemcpy(&t, static_cast<const int32_t*>(x) + r * ld + c, 4, hipMemcpyDeviceToHost); v = t; }
     set_error("%s: %llu of %lld index values outside [%lld, %lld] (first at row %lld, column %lld: %lld) [debug bounds mode]", what, res[0],
               (long long)(rows * cols), (long long)lo, (long long)hi, (long long)r, (long long)c, v);
+    return SUBGC_EINVAL;
+}
+
+int debug_check_mono(const char* who, const char* what, const char* noun, const int32_t* off, int64_t n, int64_t top, hipStream_t s) {
+    if (!off || n <= 0 || capturing(s)) return SUBGC_OK;
+    unsigned long long res[2];
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 64);
+    int rc = run_check(s, [&](unsigned long long* out) { hipLaunchKernelGGL(mono_check_kernel, dim3(grid), dim3(256), 0, s, off, n, (long long)top, out); }, res, who);
+    if (rc != SUBGC_OK) return rc;
+    if (res[0] == 0) return SUBGC_OK;
+    int32_t ab[2] = {0, 0};
+    (void)hipMemcpy(ab, off + res[1], sizeof(ab), hipMemcpyDeviceToHost);
+    set_error("%s: %s is not monotone inside [0, %lld] (%llu of %lld; first at %s %llu: %d .. %d) [debug bounds mode]", who, what, (long long)top, res[0],
+              (long long)n, noun, res[1], ab[0], ab[1]);
     return SUBGC_EINVAL;
 }
 

@@ -2,11 +2,12 @@
 // CiderScorer.compute_cider_sen_pair, external/coco_caption_patch_mRNN_cr/cider_scorer_compute_sentence.py:187-264) for a whole decode
 // batch: every candidate caption of every image against the captions of the image's k nearest training images, the m largest pair
 // scores summed, the candidates ordered by that sum.  Words are 16-bit ids (1 .. 65535; 0 never inside a sentence), an n-gram of order
-// 1 .. 4 is ONE 64-bit key (word j in bits 63-16j .. 48-16j, missing words zero: keys of different orders never coincide), so all
-// matching is exact integer comparison -- no hashing.  Arithmetic is fp64 with a summation order fixed by the inputs alone: no float
+// 1 .. 4 is ONE 64-bit key (caption.h, which also holds the caption rule of a token row and the pair walk), so all matching is exact
+// integer comparison -- no hashing.  Arithmetic is fp64 with a summation order fixed by the inputs alone: no float
 // atomics, equal inputs give equal bits.  log(df), log(#images) and the Gaussian length factor come from the host (numpy, the reference's
 // own expressions); the device adds, multiplies, takes min, divides and takes square roots.
 #include "common.h"
+#include "caption.h"
 
 namespace {
 
@@ -15,17 +16,12 @@ constexpr int kMaxK = 256;          // neighbour images per image
 constexpr int kRowWords = 64;       // words of a candidate row (the decode's T)
 constexpr int kMaxWords = 256;      // words of a corpus caption
 
-__device__ __forceinline__ int key_order(uint64_t k) {                     // 0 .. 3 for a 1- .. 4-gram: the last non-zero 16-bit lane
-    return (k & 0xffffull) ? 3 : ((k & 0xffff0000ull) ? 2 : ((k & 0xffff00000000ull) ? 1 : 0));
-}
-
 // One wave per sentence ("cook", precook + counts2vec, cider_scorer_compute_sentence.py:15-30,188-212): the <= 4 L n-gram keys, each
 // DISTINCT key once with tf = its count, in ascending key order (rank by counting: n is ~74 for a 20-word caption), weight
 // tf * (ref_len - log df) with log df found by binary search in the corpus's sorted unique keys (absent: df = 0 -> log 1 = 0), the four
 // norms (summed in key order by one lane each) and the length = the number of BIGRAMS, max(L - 1, 0) (:209-210).
-// Sentence s: CSR mode (woff != NULL) words tok[woff[s] .. woff[s+1]), all non-zero; row mode: row s of tok [S, T], words up to the
-// first id <= 0, at most row_len[s] of them (row_len NULL or negative: no limit), then -- bad != NULL -- without its trailing words
-// w with bad[w] != 0, unless every word is one (misc/utils.py:74-80).  Its list lands at keys / wts [4 * first word index ...].
+// Sentence s: CSR mode (woff != NULL) words tok[woff[s] .. woff[s+1]), all non-zero; row mode: row s of tok [S, T] by caption.h's
+// load_row, capped at row_len[s] words (row_len NULL or negative: no cap).  Its list lands at keys / wts [4 * first word index ...].
 template <int MAXW>
 __global__ __launch_bounds__(64) void cook_kernel(const void* __restrict__ tok, int tok64, const int32_t* __restrict__ woff, int T,
                                                   const int32_t* __restrict__ row_len, const uint8_t* __restrict__ bad, int bad_n,
@@ -51,18 +47,8 @@ __global__ __launch_bounds__(64) void cook_kernel(const void* __restrict__ tok, 
         for (int p = lane; p < L; p += 64) tk[p] = (uint32_t)(tok64 ? t64[start + p] : (int64_t)t32[start + p]) & 0xffffu;
     } else {                                                                // T <= 64 (checked by the entry point): one word per lane
         start = (int64_t)s * T;
-        const int64_t v = lane < T ? (tok64 ? t64[start + lane] : (int64_t)t32[start + lane]) : 0;
-        const unsigned long long stop = ~__ballot(v > 0);
-        L = stop ? __ffsll((long long)stop) - 1 : 64;
-        if (L > T) L = T;
-        if (row_len) {
-            const int r = row_len[s];
-            if (r >= 0 && r < L) L = r;
-        }
-        if (bad) {
-            const unsigned long long good = __ballot(lane < L && !(v > 0 && v < bad_n && bad[(v > 0 && v < bad_n) ? v : 0]));
-            if (good) L = 64 - __clzll((long long)good);                    // a caption of nothing but such words stays whole
-        }
+        int64_t v;
+        L = load_row(tok, tok64, T, s, bad, bad_n, lane, v, row_len ? row_len[s] : -1);
         if (lane < L) tk[lane] = (uint32_t)v & 0xffffu;
     }
     if (lane == 0) nu_sh = 0;
@@ -71,25 +57,14 @@ __global__ __launch_bounds__(64) void cook_kernel(const void* __restrict__ tok, 
     for (int o = 0; o < 4; ++o) {
         const int c = L - o;
         if (c <= 0) break;
-        for (int p = lane; p < c; p += 64) {
-            uint64_t key = (uint64_t)tk[p] << 48;
-            if (o >= 1) key |= (uint64_t)tk[p + 1] << 32;
-            if (o >= 2) key |= (uint64_t)tk[p + 2] << 16;
-            if (o >= 3) key |= (uint64_t)tk[p + 3];
-            gk[nk + p] = key;
-        }
+        for (int p = lane; p < c; p += 64) gk[nk + p] = ngram_key(tk, p, o);
         nk += c;
     }
     __syncthreads();
     int mine = 0;
     for (int i = lane; i < nk; i += 64) {
-        const uint64_t ki = gk[i];
-        int eq = 0, before = 0;
-        for (int j = 0; j < nk; ++j) {
-            const bool same = gk[j] == ki;
-            eq += same;
-            before += same && j < i;
-        }
+        int before;
+        const int eq = count_key(gk, 0, nk, i, before);
         tf[i] = before == 0 ? eq : 0;
         mine += before == 0;
     }
@@ -130,10 +105,8 @@ __global__ __launch_bounds__(64) void cook_kernel(const void* __restrict__ tok, 
 }
 
 // One workgroup per (candidate c, image i).  The candidate's cooked list sits in LDS; the captions of the image's first k neighbour
-// images are listed in neighbour order (consensus_reranking.py:155-157); thread t scores captions t, t + 256, ...: it walks the caption's
-// sorted list once (addresses do not depend on the comparisons, so the loads pipeline) while a cursor advances through the candidate's --
-// all four orders in the one pass, a matching key adds min(w_hyp, w_ref) * w_ref to its order's sum in ascending key order (sim(),
-// cider_scorer_compute_sentence.py:225-240).  The pair scores are sorted descending in LDS and the first min(m, count) are added in
+// images are listed in neighbour order (consensus_reranking.py:155-157); thread t scores captions t, t + 256, ... by
+// caption.h's cider_walk and cider_finish, all four orders in the one pass (sim(), cider_scorer_compute_sentence.py:225-240).  The pair scores are sorted descending in LDS and the first min(m, count) are added in
 // that order by one thread, as `b_s_arr.sort(reverse=True); sum(b_s_arr[:m])` does (:168-169).
 __global__ __launch_bounds__(256) void score_kernel(const uint64_t* __restrict__ ckeys, const double* __restrict__ cw,
                                                     const int32_t* __restrict__ ccnt, const int32_t* __restrict__ clen,
@@ -180,44 +153,20 @@ __global__ __launch_bounds__(256) void score_kernel(const uint64_t* __restrict__
         for (int q = 0; q < bn && p + q < max_caps; ++q) caps[p + q] = b0 + q;
     }
     const int nc = pre[k] < max_caps ? pre[k] : max_caps;
-    const double hn0 = cnorm[(int64_t)row * 4], hn1 = cnorm[(int64_t)row * 4 + 1], hn2 = cnorm[(int64_t)row * 4 + 2],
-                 hn3 = cnorm[(int64_t)row * 4 + 3];
+    const double hn[4] = {cnorm[(int64_t)row * 4], cnorm[(int64_t)row * 4 + 1], cnorm[(int64_t)row * 4 + 2], cnorm[(int64_t)row * 4 + 3]};
     const int hl = clen[row];
     __syncthreads();
     for (int j = t; j < nc; j += 256) {
         const int s = caps[j];
         const int64_t base = 4 * (int64_t)nwoff[s];
         const int nb = ncnt[s];
-        double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
-        int ia = 0;
-        uint64_t ck = na > 0 ? hk[0] : ~0ull;
-#pragma unroll 4
-        for (int ib = 0; ib < nb; ++ib) {
-            const uint64_t key = nkeys[base + ib];
-            const double w = nw[base + ib];
-            while (ck < key) {
-                ++ia;
-                ck = ia < na ? hk[ia] : ~0ull;
-            }
-            if (ck == key && ia < na) {
-                const double term = fmin(hw[ia], w) * w;
-                const int o = key_order(key);
-                v0 += o == 0 ? term : 0.0;
-                v1 += o == 1 ? term : 0.0;
-                v2 += o == 2 ? term : 0.0;
-                v3 += o == 3 ? term : 0.0;
-            }
-        }
-        const double r0 = nnorm[(int64_t)s * 4], r1 = nnorm[(int64_t)s * 4 + 1], r2 = nnorm[(int64_t)s * 4 + 2], r3 = nnorm[(int64_t)s * 4 + 3];
+        double v[4];
+        cider_walk(hk, hw, na, nkeys, nw, base, nb, v);
+        const double rn[4] = {nnorm[(int64_t)s * 4], nnorm[(int64_t)s * 4 + 1], nnorm[(int64_t)s * 4 + 2], nnorm[(int64_t)s * 4 + 3]};
         int d = hl - nlen[s];
         d = d < 0 ? -d : d;
-        const double g = gauss[d < n_gauss ? d : n_gauss - 1];
-        if (hn0 != 0.0 && r0 != 0.0) v0 /= hn0 * r0;
-        if (hn1 != 0.0 && r1 != 0.0) v1 /= hn1 * r1;
-        if (hn2 != 0.0 && r2 != 0.0) v2 /= hn2 * r2;
-        if (hn3 != 0.0 && r3 != 0.0) v3 /= hn3 * r3;
-        v0 *= g; v1 *= g; v2 *= g; v3 *= g;
-        const double score = (((v0 + v1) + v2) + v3) / 4.0 * 10.0;         // np.mean of the four orders, x 10 (:257-261)
+        cider_finish(v, hn, rn, gauss[d < n_gauss ? d : n_gauss - 1]);
+        const double score = (((v[0] + v[1]) + v[2]) + v[3]) / 4.0 * 10.0;         // np.mean of the four orders, x 10 (:257-261)
         sc[j] = score;
         if (pair_out) pair_out[(int64_t)row * pair_ld + j] = score;
     }

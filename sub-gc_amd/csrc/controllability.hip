@@ -11,27 +11,12 @@
 
 #pragma clang fp contract(off)
 
+#include "caption.h"      // after the pragma: its functions are compiled without contraction here
+
 namespace {
 
 constexpr int kWords = SUBGC_CTL_MAX_WORDS;
 constexpr int kWaves = 4;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// One WAVE reads row r of tok [rows, T], T <= 64 -> the caption's length (ids before the first id <= 0, minus trailing words w with
-// bad[w] != 0 unless every word is one: misc/utils.py:74-80, the rule of subgc_consensus_cook); v = the lane's id
-__device__ __forceinline__ int load_row(const void* __restrict__ tok, int tok64, int T, int64_t r, const uint8_t* __restrict__ bad, int bad_n,
-                                        int lane, int64_t& v) {
-    v = lane < T ? (tok64 ? static_cast<const int64_t*>(tok)[r * T + lane] : (int64_t)static_cast<const int32_t*>(tok)[r * T + lane]) : 0;
-    const unsigned long long stop = ~__ballot(v > 0);
-    int L = stop ? __ffsll((long long)stop) - 1 : 64;
-    if (L > T) L = T;
-    if (bad) {
-        const unsigned long long good = __ballot(lane < L && !(v > 0 && v < bad_n && bad[(v > 0 && v < bad_n) ? v : 0]));
-        if (good) L = 64 - __clzll((long long)good);
-    }
-    return L;
-}
 
 // the smallest value over the 64 lanes (all active)
 __device__ __forceinline__ double wave_min_f64(double v) {
@@ -202,41 +187,6 @@ __global__ __launch_bounds__(kWaves * 64) void noun_iou_kernel(const void* __res
     }
 }
 
-// debug bounds mode: 0 <= off[i] <= off[i+1] <= top for every i < n; out[0] = violations, out[1] = the first position
-__global__ __launch_bounds__(256) void check_mono_kernel(const int32_t* __restrict__ off, int n, int top, unsigned long long* __restrict__ out) {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const int a = off[i], b = off[i + 1];
-        if (a < 0 || b < a || b > top) {
-            atomicAdd(out, 1ull);
-            atomicMin(out + 1, (unsigned long long)i);
-        }
-    }
-}
-
-int check_mono(const char* who, const char* what, const int32_t* off, int n, int top, hipStream_t s) {
-    if (!subgc::debug_bounds() || n <= 0) return SUBGC_OK;
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return SUBGC_OK; }
-    if (st != hipStreamCaptureStatusNone) return SUBGC_OK;
-    unsigned long long* out = nullptr;
-    unsigned long long res[2] = {0ull, ~0ull};
-    if (hipMalloc(&out, sizeof(res)) != hipSuccess) { subgc::set_error("%s: debug check cannot allocate its result word", who); return SUBGC_ELAUNCH; }
-    bool ok = hipMemcpyAsync(out, res, sizeof(res), hipMemcpyHostToDevice, s) == hipSuccess;
-    if (ok) {
-        hipLaunchKernelGGL(check_mono_kernel, dim3((int)subgc::cdiv(n, 256) < 64 ? (int)subgc::cdiv(n, 256) : 64), dim3(256), 0, s, off, n, top, out);
-        ok = hipGetLastError() == hipSuccess;
-    }
-    ok = ok && hipMemcpyAsync(res, out, sizeof(res), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    (void)hipFree(out);
-    if (!ok) { subgc::set_error("%s: debug check failed to run: %s", who, hipGetErrorString(hipGetLastError())); return SUBGC_ELAUNCH; }
-    if (res[0] == 0) return SUBGC_OK;
-    int32_t ab[2] = {0, 0};
-    (void)hipMemcpy(ab, off + res[1], sizeof(ab), hipMemcpyDeviceToHost);
-    subgc::set_error("%s: %s is not monotone inside [0, %d] (%llu positions; first at %llu: %d .. %d) [debug bounds mode]", who, what, top, res[0],
-                     res[1], ab[0], ab[1]);
-    return SUBGC_EINVAL;
-}
-
 }  // namespace
 
 SUBGC_API int subgc_control_noun_iou(const void* tok, int tok64, int T, const uint8_t* bad, int bad_n, int rows, const int32_t* tok_noun, int n_tok_noun,
@@ -254,9 +204,9 @@ SUBGC_API int subgc_control_noun_iou(const void* tok, int tok64, int T, const ui
                   "control_noun_iou: null pointer");
     hipStream_t s = (hipStream_t)stream;
     SUBGC_DEBUG_RANGE(row_group, 4, 1, rows, rows, 0, (int64_t)n_groups - 1, -1, "control_noun_iou: row_group (ground-truth group of every row)", s);
-    if (int rc = check_mono("control_noun_iou", "pair_off (pairs of the rows)", pair_off, rows, n_pairs, s)) return rc;
-    if (int rc = check_mono("control_noun_iou", "gcap_off (CSR caption offsets of the groups)", gcap_off, n_groups, n_caps, s)) return rc;
-    if (int rc = check_mono("control_noun_iou", "gn_off (CSR vector-word offsets of the captions)", gn_off, n_caps, n_gn, s)) return rc;
+    SUBGC_DEBUG_MONO("control_noun_iou", "pair_off (pairs of the rows)", "position", pair_off, rows, n_pairs, s);
+    SUBGC_DEBUG_MONO("control_noun_iou", "gcap_off (CSR caption offsets of the groups)", "position", gcap_off, n_groups, n_caps, s);
+    SUBGC_DEBUG_MONO("control_noun_iou", "gn_off (CSR vector-word offsets of the captions)", "position", gn_off, n_caps, n_gn, s);
     SUBGC_DEBUG_RANGE(gn, 4, 1, n_gn, n_gn, 0, (int64_t)n_noun - 1, -1, "control_noun_iou: gn (vector rows of the ground-truth words)", s);
     SUBGC_DEBUG_RANGE(tok_noun, 4, 1, n_tok_noun, n_tok_noun, 0, (int64_t)n_noun - 1, -1, "control_noun_iou: tok_noun (vector row of every word id)", s);
     hipLaunchKernelGGL(noun_iou_kernel, dim3(rows), dim3(kWaves * 64), 0, s, tok, tok64, T, bad, bad_n, tok_noun, n_tok_noun, vec, norm, n_noun, d, row_group,

@@ -4,11 +4,12 @@
 // grid.  Three kernels: the best n_best rows of a draw by score (select), the distinct captions of a whole draw (distinct) and, over the
 // selected rows, word / unigram / bigram counts, the novel count against a sorted training-caption index and the n_best sentence
 // BLEU-4 values with their mean (best).  A caption is its tokens before the first id <= 0, trimmed like decode_sequence does when
-// remove_bad_endings is on (the rule of subgc_consensus_cook); words are 16-bit ids, an n-gram one 64-bit key as in consensus.hip, so
+// remove_bad_endings is on (caption.h's load_row); words are 16-bit ids, an n-gram one 64-bit key (caption.h's ngram_key), so
 // every comparison is exact integer comparison -- the one hash (distinct) only pre-filters and is confirmed on the tokens.  Counts are
 // integers (LDS integer adds: order-free), the BLEU arithmetic is fp64 in the reference's own order with no float atomics: equal inputs
 // give equal bits.
 #include "common.h"
+#include "caption.h"
 
 namespace {
 
@@ -22,10 +23,6 @@ __device__ __forceinline__ uint32_t order_key(float x) {         // a < b  <=>  
     if (b == 0x80000000u) b = 0u;
     return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
 }
-__device__ __forceinline__ int key_order(uint64_t k) {                     // 0 .. 3 for a 1- .. 4-gram: the last non-zero 16-bit lane
-    return (k & 0xffffull) ? 3 : ((k & 0xffff0000ull) ? 2 : ((k & 0xffff00000000ull) ? 1 : 0));
-}
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // Where a set lives: a = the image's first row, n = its rows, d0 = the draw's first slot, m = the draw's length (<= kMaxDraw; 0 for an
 // image without rows).  Every field is clamped into what the buffers hold, whatever the index tensors say (debug bounds mode reports).
@@ -45,26 +42,6 @@ __device__ __forceinline__ SetView set_view(const int32_t* __restrict__ seg, int
         v.m = v.n > 0 ? (d1 - d0 < kMaxDraw ? d1 - d0 : kMaxDraw) : 0;
     }
     return v;
-}
-
-__device__ __forceinline__ int64_t tok_at(const void* __restrict__ tok, int tok64, int64_t i) {
-    return tok64 ? static_cast<const int64_t*>(tok)[i] : (int64_t)static_cast<const int32_t*>(tok)[i];
-}
-
-// One WAVE (all 64 lanes) reads row r of tok [rows, T], T <= 64: -> the caption's length (ids before the first id <= 0, minus trailing
-// words w with bad[w] != 0 unless every word is one: misc/utils.py:74-80); w = the lane's word where lane < length.
-__device__ __forceinline__ int load_row(const void* __restrict__ tok, int tok64, int T, int64_t r, const uint8_t* __restrict__ bad, int bad_n,
-                                        int lane, uint32_t& w) {
-    const int64_t v = lane < T ? tok_at(tok, tok64, r * T + lane) : 0;
-    const unsigned long long stop = ~__ballot(v > 0);
-    int L = stop ? __ffsll((long long)stop) - 1 : 64;
-    if (L > T) L = T;
-    if (bad) {
-        const unsigned long long good = __ballot(lane < L && !(v > 0 && v < bad_n && bad[(v > 0 && v < bad_n) ? v : 0]));
-        if (good) L = 64 - __clzll((long long)good);
-    }
-    w = (uint32_t)v & 0xffffu;
-    return L;
 }
 
 __device__ __forceinline__ uint64_t mix64(uint64_t x) {
@@ -120,9 +97,9 @@ __global__ __launch_bounds__(256) void distinct_kernel(const void* __restrict__ 
     if (t == 0) total = 0;
     for (int j = wave; j < v.m; j += 4) {
         const int r = v.a + clampi(draw[v.d0 + j], 0, v.n - 1);
-        uint32_t w;
-        const int L = load_row(tok, tok64, T, r, bad, bad_n, lane, w);
-        uint64_t h = lane < L ? mix64(((uint64_t)(lane + 1) << 16) | w) : 0ull;
+        int64_t id;
+        const int L = load_row(tok, tok64, T, r, bad, bad_n, lane, id);
+        uint64_t h = lane < L ? mix64(((uint64_t)(lane + 1) << 16) | ((uint32_t)id & 0xffffu)) : 0ull;
         for (int d = 32; d > 0; d >>= 1) h ^= __shfl_xor((unsigned long long)h, d);
         if (lane == 0) {
             hs[j] = h;
@@ -212,9 +189,9 @@ __global__ __launch_bounds__(256) void best_kernel(const void* __restrict__ tok,
     const SetView v = set_view(seg, I, rows, set_img, nullptr, 0, s);
     const int nsel = v.n > 0 ? clampi(o[SUBGC_DIV_SELECTED], 0, n_best) : 0;
     for (int q = wave; q < nsel; q += 4) {
-        uint32_t w;
-        const int L = load_row(tok, tok64, T, v.a + clampi(o[kCols + q], 0, v.n - 1), bad, bad_n, lane, w);
-        tk[q * kRowWords + lane] = lane < L ? w : 0u;
+        int64_t id;
+        const int L = load_row(tok, tok64, T, v.a + clampi(o[kCols + q], 0, v.n - 1), bad, bad_n, lane, id);
+        tk[q * kRowWords + lane] = lane < L ? (uint32_t)id & 0xffffu : 0u;
         if (lane == 0) Ls[q] = L;
     }
     if (t < kMaxBest * 4) correct[t] = 0;
@@ -239,13 +216,7 @@ __global__ __launch_bounds__(256) void best_kernel(const void* __restrict__ tok,
         if (p + 1 < L) bl[boff[q] + p] = (w[p] << 16) | w[p + 1];
         int base = goff[q];
         for (int k = 0; k < 4; ++k) {
-            if (p + k < L) {
-                uint64_t key = (uint64_t)w[p] << 48;
-                if (k >= 1) key |= (uint64_t)w[p + 1] << 32;
-                if (k >= 2) key |= (uint64_t)w[p + 2] << 16;
-                if (k >= 3) key |= (uint64_t)w[p + 3];
-                gk[base + p] = key;
-            }
+            if (p + k < L) gk[base + p] = ngram_key(w, p, k);
             base += L > k ? L - k : 0;
         }
     }
@@ -284,12 +255,8 @@ __global__ __launch_bounds__(256) void best_kernel(const void* __restrict__ tok,
             int q = 0;
             while (goff[q + 1] <= g) ++q;
             const uint64_t key = gk[g];
-            int c = 0, before = 0;
-            for (int j = goff[q]; j < goff[q + 1]; ++j) {
-                const bool same = gk[j] == key;
-                c += same;
-                before += same && j < g;
-            }
+            int before;
+            const int c = count_key(gk, goff[q], goff[q + 1], g, before);
             if (before) continue;
             int mx = 0;
             for (int r = 0; r < nsel; ++r) {
@@ -307,13 +274,7 @@ __global__ __launch_bounds__(256) void best_kernel(const void* __restrict__ tok,
         double val = 0.0;
         if (bleu && t < nsel) {
             const double small = 1e-9, tiny = 1e-15;
-            const int testlen = Ls[t];
-            int best_d = 1 << 30, reflen = 0;                               // min((abs(l - testlen), l)): the closest, the shorter on a tie
-            for (int r = 0; r < nsel; ++r) {
-                if (r == t) continue;
-                const int l = Ls[r], d = l > testlen ? l - testlen : testlen - l;
-                if (d < best_d || (d == best_d && l < reflen)) { best_d = d; reflen = l; }
-            }
+            const int testlen = Ls[t], reflen = closest_len(Ls, nsel, t, testlen);         // the other selected sentences are the references
             double prod = 1.0;
             for (int k = 0; k < 4; ++k) {
                 const int guess = testlen - k > 0 ? testlen - k : 0;
@@ -338,23 +299,12 @@ __global__ __launch_bounds__(256) void best_kernel(const void* __restrict__ tok,
     }
 }
 
-// debug bounds mode: block 0 walks seg (0 <= seg[i] <= seg[i+1] <= rows), block 1 + s the draw of set s (0 <= entry < rows of its image).
-// out[0] = violations, out[1] = the smallest of (kind << 62 | set << 20 | position), kind 0 = seg, 1 = draw
-__global__ __launch_bounds__(256) void check_kernel(const int32_t* __restrict__ seg, int I, int rows, const int32_t* __restrict__ set_img,
-                                                    const int32_t* __restrict__ set_off, const int32_t* __restrict__ draw, int n_draw,
-                                                    unsigned long long* __restrict__ out) {
-    if (blockIdx.x == 0) {
-        for (int i = threadIdx.x; i < I; i += 256) {
-            const int a = seg[i], b = seg[i + 1];
-            if (a < 0 || b < a || b > rows) {
-                atomicAdd(out, 1ull);
-                atomicMin(out + 1, (unsigned long long)i);
-            }
-        }
-        return;
-    }
-    if (!set_off) return;
-    const int s = blockIdx.x - 1;
+// debug bounds mode: block s walks the draw of set s (0 <= entry < rows of its image); out[0] = violations, out[1] = the smallest of
+// (set << 20 | position)
+__global__ __launch_bounds__(256) void check_draw_kernel(const int32_t* __restrict__ seg, int I, const int32_t* __restrict__ set_img,
+                                                         const int32_t* __restrict__ set_off, const int32_t* __restrict__ draw, int n_draw,
+                                                         unsigned long long* __restrict__ out) {
+    const int s = blockIdx.x;
     const int img = clampi(set_img[s], 0, I - 1);
     const int n = seg[img + 1] - seg[img];
     const int d0 = clampi(set_off[s], 0, n_draw), d1 = clampi(set_off[s + 1], d0, n_draw);
@@ -362,38 +312,24 @@ __global__ __launch_bounds__(256) void check_kernel(const int32_t* __restrict__ 
         const int d = draw[d0 + j];
         if (d < 0 || d >= n) {
             atomicAdd(out, 1ull);
-            atomicMin(out + 1, (1ull << 62) | ((unsigned long long)s << 20) | (unsigned long long)(j < (1 << 20) - 1 ? j : (1 << 20) - 1));
+            atomicMin(out + 1, ((unsigned long long)s << 20) | (unsigned long long)(j < (1 << 20) - 1 ? j : (1 << 20) - 1));
         }
     }
 }
 
+// set_img, then seg, then -- where the launch reads one (set_off != NULL) -- the draws
 int check_sets(const char* who, const int32_t* seg, int I, int rows, const int32_t* set_img, const int32_t* set_off, const int32_t* draw,
                int n_sets, int n_draw, hipStream_t s) {
-    if (!subgc::debug_bounds()) return SUBGC_OK;
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return SUBGC_OK; }
-    if (st != hipStreamCaptureStatusNone) return SUBGC_OK;
+    if (!subgc::debug_bounds() || subgc::capturing(s)) return SUBGC_OK;
     if (int rc = subgc::debug_check_range(set_img, 4, 1, n_sets, n_sets, 0, (int64_t)I - 1, -1, "diversity: set_img (image of every set)", s)) return rc;
-    unsigned long long* out = nullptr;
-    unsigned long long res[2] = {0ull, ~0ull};
-    if (hipMalloc(&out, sizeof(res)) != hipSuccess) { subgc::set_error("%s: debug check cannot allocate its result word", who); return SUBGC_ELAUNCH; }
-    bool ok = hipMemcpyAsync(out, res, sizeof(res), hipMemcpyHostToDevice, s) == hipSuccess;
-    if (ok) {
-        hipLaunchKernelGGL(check_kernel, dim3(1 + (set_off ? n_sets : 0)), dim3(256), 0, s, seg, I, rows, set_img, set_off, draw, n_draw, out);
-        ok = hipGetLastError() == hipSuccess;
-    }
-    ok = ok && hipMemcpyAsync(res, out, sizeof(res), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    (void)hipFree(out);
-    if (!ok) { subgc::set_error("%s: debug check failed to run: %s", who, hipGetErrorString(hipGetLastError())); return SUBGC_ELAUNCH; }
+    if (int rc = subgc::debug_check_mono(who, "seg (row boundaries of the images)", "image", seg, I, rows, s)) return rc;
+    if (!set_off) return SUBGC_OK;
+    unsigned long long res[2];
+    if (int rc = subgc::run_check(s, [&](unsigned long long* out) {
+            hipLaunchKernelGGL(check_draw_kernel, dim3(n_sets), dim3(256), 0, s, seg, I, set_img, set_off, draw, n_draw, out);
+        }, res, who)) return rc;
     if (res[0] == 0) return SUBGC_OK;
-    if (!(res[1] >> 62)) {
-        int32_t ab[2] = {0, 0};
-        (void)hipMemcpy(ab, seg + res[1], sizeof(ab), hipMemcpyDeviceToHost);
-        subgc::set_error("%s: seg (row boundaries of the images) is not monotone inside [0, %d] (first at image %llu: %d .. %d) [debug bounds mode]", who,
-                         rows, res[1], ab[0], ab[1]);
-        return SUBGC_EINVAL;
-    }
-    const int set = (int)((res[1] >> 20) & 0xffffffffull), pos = (int)(res[1] & 0xfffffull);
+    const int set = (int)(res[1] >> 20), pos = (int)(res[1] & 0xfffffull);
     int32_t off = 0, val = 0, img = 0, ab[2] = {0, 0};
     (void)hipMemcpy(&off, set_off + set, 4, hipMemcpyDeviceToHost);
     (void)hipMemcpy(&val, draw + off + pos, 4, hipMemcpyDeviceToHost);

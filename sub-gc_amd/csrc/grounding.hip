@@ -10,27 +10,12 @@
 
 #pragma clang fp contract(off)
 
+#include "caption.h"      // after the pragma: its functions are compiled without contraction here
+
 namespace {
 
 constexpr int kWords = SUBGC_GRD_MAX_WORDS;
 constexpr int kObj = SUBGC_GRD_MAX_OBJ;
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// One WAVE reads row r of tok [rows, T], T <= 64 -> the caption's length (ids before the first id <= 0, minus trailing words w with
-// bad[w] != 0 unless every word is one: misc/utils.py:74-80, the rule of subgc_consensus_cook); v = the lane's id
-__device__ __forceinline__ int load_row(const void* __restrict__ tok, int tok64, int T, int64_t r, const uint8_t* __restrict__ bad, int bad_n,
-                                        int lane, int64_t& v) {
-    v = lane < T ? (tok64 ? static_cast<const int64_t*>(tok)[r * T + lane] : (int64_t)static_cast<const int32_t*>(tok)[r * T + lane]) : 0;
-    const unsigned long long stop = ~__ballot(v > 0);
-    int L = stop ? __ffsll((long long)stop) - 1 : 64;
-    if (L > T) L = T;
-    if (bad) {
-        const unsigned long long good = __ballot(lane < L && !(v > 0 && v < bad_n && bad[(v > 0 && v < bad_n) ? v : 0]));
-        if (good) L = 64 - __clzll((long long)good);
-    }
-    return L;
-}
 
 // One wave per batch image; lane j = word position j.  The grounded words are compacted in word order by a ballot prefix count.
 __global__ __launch_bounds__(64) void material_kernel(const void* __restrict__ tok, int tok64, int T, const uint8_t* __restrict__ bad, int bad_n, int rows,
@@ -173,41 +158,6 @@ __global__ __launch_bounds__(64) void score_kernel(const int32_t* __restrict__ m
     for (int q = g0 + 64 + lane; q < g1; q += 64) rec[q] = SUBGC_GRD_NONE;
 }
 
-// debug bounds mode: 0 <= off[i] <= off[i+1] <= top for every i < n; out[0] = violations, out[1] = the first position
-__global__ __launch_bounds__(256) void check_mono_kernel(const int32_t* __restrict__ off, int n, int top, unsigned long long* __restrict__ out) {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-        const int a = off[i], b = off[i + 1];
-        if (a < 0 || b < a || b > top) {
-            atomicAdd(out, 1ull);
-            atomicMin(out + 1, (unsigned long long)i);
-        }
-    }
-}
-
-int check_mono(const char* who, const char* what, const int32_t* off, int n, int top, hipStream_t s) {
-    if (!subgc::debug_bounds() || n <= 0) return SUBGC_OK;
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return SUBGC_OK; }
-    if (st != hipStreamCaptureStatusNone) return SUBGC_OK;
-    unsigned long long* out = nullptr;
-    unsigned long long res[2] = {0ull, ~0ull};
-    if (hipMalloc(&out, sizeof(res)) != hipSuccess) { subgc::set_error("%s: debug check cannot allocate its result word", who); return SUBGC_ELAUNCH; }
-    bool ok = hipMemcpyAsync(out, res, sizeof(res), hipMemcpyHostToDevice, s) == hipSuccess;
-    if (ok) {
-        hipLaunchKernelGGL(check_mono_kernel, dim3((int)subgc::cdiv(n, 256) < 64 ? (int)subgc::cdiv(n, 256) : 64), dim3(256), 0, s, off, n, top, out);
-        ok = hipGetLastError() == hipSuccess;
-    }
-    ok = ok && hipMemcpyAsync(res, out, sizeof(res), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    (void)hipFree(out);
-    if (!ok) { subgc::set_error("%s: debug check failed to run: %s", who, hipGetErrorString(hipGetLastError())); return SUBGC_ELAUNCH; }
-    if (res[0] == 0) return SUBGC_OK;
-    int32_t ab[2] = {0, 0};
-    (void)hipMemcpy(ab, off + res[1], sizeof(ab), hipMemcpyDeviceToHost);
-    subgc::set_error("%s: %s is not monotone inside [0, %d] (%llu positions; first at %llu: %d .. %d) [debug bounds mode]", who, what, top, res[0],
-                     res[1], ab[0], ab[1]);
-    return SUBGC_EINVAL;
-}
-
 }  // namespace
 
 SUBGC_API int subgc_grounding_material(const void* tok, int tok64, int T, const uint8_t* bad, int bad_n, int rows, const int32_t* seg,
@@ -224,8 +174,8 @@ SUBGC_API int subgc_grounding_material(const void* tok, int tok64, int T, const 
                       (n_boxes == 0 || boxes),
                   "grounding_material: null pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (int rc = check_mono("grounding_material", "seg (row boundaries of the images)", seg, I, rows, s)) return rc;
-    if (int rc = check_mono("grounding_material", "box_off (box rows of the images)", box_off, I, n_boxes, s)) return rc;
+    SUBGC_DEBUG_MONO("grounding_material", "seg (row boundaries of the images)", "position", seg, I, rows, s);
+    SUBGC_DEBUG_MONO("grounding_material", "box_off (box rows of the images)", "position", box_off, I, n_boxes, s);
     // a pick is image-local; 8192 rows per image is the ranking launch's own limit, so [0, rows) is the check that needs no second table
     SUBGC_DEBUG_RANGE(pick, 4, 1, I, I, 0, rows > 0 ? (int64_t)rows - 1 : 0, -1, "grounding_material: pick (chosen caption of every image)", s);
     SUBGC_DEBUG_RANGE(node, 4, I, T1, T1, 0, n_boxes > 0 ? (int64_t)n_boxes - 1 : 0, -1, "grounding_material: node (box row of every word position)", s);
@@ -250,12 +200,12 @@ SUBGC_API int subgc_grounding_score(const int32_t* mat_n, const int32_t* mat_cls
                   "grounding_score: null pointer");
     hipStream_t s = (hipStream_t)stream;
     SUBGC_DEBUG_RANGE(img_ref, 4, 1, I, I, 0, (int64_t)n_ref - 1, -1, "grounding_score: img_ref (reference image of every batch image)", s);
-    if (int rc = check_mono("grounding_score", "pair_off (pairs of the batch images)", pair_off, I, n_pairs, s)) return rc;
-    if (int rc = check_mono("grounding_score", "cap_off (CSR caption offsets)", cap_off, n_ref, n_caps, s)) return rc;
-    if (int rc = check_mono("grounding_score", "obj_off (CSR object offsets)", obj_off, n_caps, n_obj, s)) return rc;
-    if (int rc = check_mono("grounding_score", "ex_off (CSR excluded-lemma offsets)", ex_off, n_caps, n_ex, s)) return rc;
-    if (int rc = check_mono("grounding_score", "prec_off (precision event offsets)", prec_off, n_pairs, n_prec, s)) return rc;
-    if (int rc = check_mono("grounding_score", "rec_off (recall event offsets)", rec_off, n_pairs, n_rec, s)) return rc;
+    SUBGC_DEBUG_MONO("grounding_score", "pair_off (pairs of the batch images)", "position", pair_off, I, n_pairs, s);
+    SUBGC_DEBUG_MONO("grounding_score", "cap_off (CSR caption offsets)", "position", cap_off, n_ref, n_caps, s);
+    SUBGC_DEBUG_MONO("grounding_score", "obj_off (CSR object offsets)", "position", obj_off, n_caps, n_obj, s);
+    SUBGC_DEBUG_MONO("grounding_score", "ex_off (CSR excluded-lemma offsets)", "position", ex_off, n_caps, n_ex, s);
+    SUBGC_DEBUG_MONO("grounding_score", "prec_off (precision event offsets)", "position", prec_off, n_pairs, n_prec, s);
+    SUBGC_DEBUG_MONO("grounding_score", "rec_off (recall event offsets)", "position", rec_off, n_pairs, n_rec, s);
     hipLaunchKernelGGL(score_kernel, dim3(n_pairs), dim3(64), 0, s, mat_n, mat_cls, mat_box, ld_m, I, img_ref, n_ref, pair_off, n_pairs, cap_off, n_caps,
                        obj_off, obj_cls, obj_idx, obj_box, n_obj, ex_off, ex_lemma, n_ex, class_lemma, n_class, iou_thresh, prec_off, prec, n_prec,
                        rec_off, rec, n_rec);

@@ -123,49 +123,34 @@ def call(name, *args):
         raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
 
 
-_FN_METRICS = {}  # the entry points of subgc_metrics_hip.h: a cache of their own, so that neither invoker reaches the other's header
+def _call_in(header, cache, name, args):
+    """`call` for the entry points of one of the other headers: a cache per header, so that no invoker reaches another's declarations."""
+    fn = cache.get(name)
+    if fn is None:
+        if name not in parse_header(header):
+            raise SubgcError(f"{name} is not declared in {os.path.basename(header)}")
+        fn = cache[name] = getattr(lib(), name)
+    rc = fn(*args)
+    if rc != 0:
+        raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
+
+
+_FN_METRICS, _FN_GROUNDING, _FN_CONTROLLABILITY = {}, {}, {}
 
 
 def call_metrics(name, *args):
     """`call` for the entry points of subgc_metrics_hip.h."""
-    fn = _FN_METRICS.get(name)
-    if fn is None:
-        if name not in parse_header(METRICS_HEADER):
-            raise SubgcError(f"{name} is not declared in subgc_metrics_hip.h")
-        fn = _FN_METRICS[name] = getattr(lib(), name)
-    rc = fn(*args)
-    if rc != 0:
-        raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
-
-
-_FN_GROUNDING = {}  # the entry points of subgc_grounding_hip.h
+    _call_in(METRICS_HEADER, _FN_METRICS, name, args)
 
 
 def call_grounding(name, *args):
     """`call` for the entry points of subgc_grounding_hip.h."""
-    fn = _FN_GROUNDING.get(name)
-    if fn is None:
-        if name not in parse_header(GROUNDING_HEADER):
-            raise SubgcError(f"{name} is not declared in subgc_grounding_hip.h")
-        fn = _FN_GROUNDING[name] = getattr(lib(), name)
-    rc = fn(*args)
-    if rc != 0:
-        raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
-
-
-_FN_CONTROLLABILITY = {}  # the entry points of subgc_controllability_hip.h
+    _call_in(GROUNDING_HEADER, _FN_GROUNDING, name, args)
 
 
 def call_controllability(name, *args):
     """`call` for the entry points of subgc_controllability_hip.h."""
-    fn = _FN_CONTROLLABILITY.get(name)
-    if fn is None:
-        if name not in parse_header(CONTROLLABILITY_HEADER):
-            raise SubgcError(f"{name} is not declared in subgc_controllability_hip.h")
-        fn = _FN_CONTROLLABILITY[name] = getattr(lib(), name)
-    rc = fn(*args)
-    if rc != 0:
-        raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
+    _call_in(CONTROLLABILITY_HEADER, _FN_CONTROLLABILITY, name, args)
 
 
 FAM = {"gemm": 1, "attn": 2, "lstm": 3, "gcn": 4, "pool": 5, "softmax": 6}
