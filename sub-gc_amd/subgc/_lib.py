@@ -24,6 +24,8 @@ METRICS_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include"
 GROUNDING_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_grounding_hip.h")
 # the set-controllability score (subgc_control_*): the fourth header, same arrangement
 CONTROLLABILITY_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_controllability_hip.h")
+# the label-smoothed language loss (subgc_row_lse_sum_f32, subgc_smoothed_*): the fifth header, same arrangement
+CRITERION_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_criterion_hip.h")
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -93,7 +95,8 @@ def lib():
         _protos = parse_header()
         for hdr, protos in (("subgc_hip.h", _protos), ("subgc_metrics_hip.h", parse_header(METRICS_HEADER)),
                             ("subgc_grounding_hip.h", parse_header(GROUNDING_HEADER)),
-                            ("subgc_controllability_hip.h", parse_header(CONTROLLABILITY_HEADER))):
+                            ("subgc_controllability_hip.h", parse_header(CONTROLLABILITY_HEADER)),
+                            ("subgc_criterion_hip.h", parse_header(CRITERION_HEADER))):
             for name, (ret, args) in protos.items():
                 try:
                     fn = getattr(L, name)
@@ -135,7 +138,7 @@ def _call_in(header, cache, name, args):
         raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
 
 
-_FN_METRICS, _FN_GROUNDING, _FN_CONTROLLABILITY = {}, {}, {}
+_FN_METRICS, _FN_GROUNDING, _FN_CONTROLLABILITY, _FN_CRITERION = {}, {}, {}, {}
 
 
 def call_metrics(name, *args):
@@ -151,6 +154,11 @@ def call_grounding(name, *args):
 def call_controllability(name, *args):
     """`call` for the entry points of subgc_controllability_hip.h."""
     _call_in(CONTROLLABILITY_HEADER, _FN_CONTROLLABILITY, name, args)
+
+
+def call_criterion(name, *args):
+    """`call` for the entry points of subgc_criterion_hip.h."""
+    _call_in(CRITERION_HEADER, _FN_CRITERION, name, args)
 
 
 FAM = {"gemm": 1, "attn": 2, "lstm": 3, "gcn": 4, "pool": 5, "softmax": 6}

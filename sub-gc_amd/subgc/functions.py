@@ -627,6 +627,26 @@ class MaskedNLLFn(Function):
         return ops.masked_nll_bwd(target, mask, scratch, dloss.contiguous(), S, T, V), None, None
 
 
+class SmoothedNLLFn(Function):
+    """LabelSmoothing (misc/utils.py:126-156): (logp [S,T,V], target, mask, smoothing) -> loss; d(logp) = -g * true_dist, dense."""
+
+    @staticmethod
+    def forward(ctx, logp, target, mask, smoothing):
+        logp = logp.contiguous()
+        S, T, V = logp.shape
+        _, slp = ops.row_lse_sum(logp.view(S * T, V), raw=False)
+        loss, scratch = ops.smoothed_nll_fwd(logp, target, mask, slp, smoothing)
+        ctx.save_for_backward(target, mask, scratch)
+        ctx.shape, ctx.smoothing = logp.shape, smoothing
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        target, mask, scratch = ctx.saved_tensors
+        S, T, V = ctx.shape
+        return ops.smoothed_nll_bwd(target, mask, scratch, dloss.contiguous(), ctx.smoothing, S, T, V), None, None, None
+
+
 # ------------------------------------------------------------------------------- decoder
 DIRECT_GRADS = True               # accumulate parameter gradients straight into existing .grad buffers
 DEFER_DU = True                   # per-sentence attention sets: d(u) formed once after the BPTT loop (subgc_attn_du_accum) instead of read-modify-written per step
@@ -995,14 +1015,19 @@ class DecoderFn(Function):
                        step_c_att=C1[1:].clone(), step_c_lang=C2[1:].clone(), step_alpha=AL.clone(),
                        step_logp=logits3.permute(1, 0, 2).clone(), fed_tokens=tokens[:, :T].t().clone())
         crit = meta.get("crit")                      # (target [S,T] view, mask [S,T] view): criterion fused in
-        if crit is not None:
+        smoothing = meta.get("smoothing", 0.0)       # > 0: LabelSmoothing (misc/utils.py:126-156) in the place of LanguageModelCriterion
+        if crit is not None and smoothing > 0:
+            # rows after the early break are zero rows (`active`): lp = 0, so a masked-in one adds m * H, as in the reference
+            _, slp = ops.row_lse_sum(logits, raw=False)
+            loss, nll_scratch = ops.smoothed_nll_fwd(logits.view(S, T, V1), crit[0], crit[1], slp, smoothing)
+        elif crit is not None:
             loss, nll_scratch = ops.masked_nll_fwd(logits.view(S, T, V1), crit[0], crit[1])
         else:
             loss, nll_scratch = torch.zeros((), device=dev), None
         ctx.meta = (N, scale, S, T, R, E, A, V1)
         ctx.masks = (k_xt, k_out)
         ctx.pr = pr
-        ctx.crit = crit
+        ctx.crit, ctx.smoothing = crit, smoothing
         ctx.nll_scratch = nll_scratch
         ctx.params, ctx.W, ctx.bf = P, W, bf
         ctx.set_materialize_grads(False)
@@ -1059,14 +1084,20 @@ class DecoderFn(Function):
             for j in (i, also):
                 ops.copy2d(tmp, out_for(j).view(1, -1), accumulate=acc[j])
 
+        def crit_bwd(dst_):                               # d(logits) of the fused criterion: NLL, or its smoothed twin
+            if ctx.smoothing > 0:
+                return ops.smoothed_logsoftmax_bwd(logp, ctx.crit[0], ctx.crit[1], ctx.nll_scratch, dloss.contiguous(), ctx.smoothing, dst_, active,
+                                                   S, T, V1)
+            return ops.nll_logsoftmax_bwd(logp, ctx.crit[0], ctx.crit[1], ctx.nll_scratch, dloss.contiguous(), dst_, active, S, T, V1)
+
         if ctx.crit is not None and dloss is not None and dout is None:
             # d(logits) only feeds the logit layer's two gradient GEMMs and its bias sum: written bf16 under compute_dtype = bf16
             dlogits = ops.empty_b16(S * T, V1, dev) if bf else new(S * T, V1)
-            ops.nll_logsoftmax_bwd(logp, ctx.crit[0], ctx.crit[1], ctx.nll_scratch, dloss.contiguous(), dlogits, active, S, T, V1)
+            crit_bwd(dlogits)
         elif dout is not None:
             dlogits = new(S * T, V1)
             if ctx.crit is not None and dloss is not None:   # the log-probabilities were ALSO used elsewhere
-                ops.nll_logsoftmax_bwd(logp, ctx.crit[0], ctx.crit[1], ctx.nll_scratch, dloss.contiguous(), dlogits, active, S, T, V1)
+                crit_bwd(dlogits)
                 extra = new(S * T, V1)
                 ops.log_softmax_rows_bwd(logp, dout.contiguous().view(S * T, V1), extra, active)
                 dlogits.add_(extra)

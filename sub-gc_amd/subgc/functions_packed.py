@@ -60,7 +60,7 @@ def live_plan(labels, mask_t):
 
 
 class PackedDecoderLossFn(Function):
-    """(labels, fc_in, X_nodes, lens, idx, img, params...) -> masked NLL (scalar)."""
+    """(labels, fc_in, X_nodes, lens, idx, img, params...) -> masked NLL (scalar); with meta["smoothing"] > 0 the label-smoothed loss."""
 
     @staticmethod
     def forward(ctx, meta, labels, fc_in, X_nodes, lens, idx, img, *P):
@@ -169,14 +169,23 @@ class PackedDecoderLossFn(Function):
         elif T_live > 0:
             op = ot[T_live - 1]
             ops.gemm(Hout[op:rows], W[21], logits[op:rows], tb=True, bias=lg_b)
-        lse = ops.row_lse(logits[:rows])                                  # log_softmax without the write: the loss needs lse and one logit per row
+        smoothing = meta.get("smoothing", 0.0)                            # > 0: LabelSmoothing (misc/utils.py:126-156)
+        if smoothing > 0:
+            lse, slp = ops.row_lse_sum(logits[:rows])                     # the same row pass, one more scalar per row: sum_c (x - lse)
+        else:
+            lse = ops.row_lse(logits[:rows])                              # log_softmax without the write: the loss needs lse and one logit per row
         # criterion over the packed rows: row ot[t] + s  <->  (sentence perm[s], step t); the denominator is the sum of ALL mask
         # entries (dead ones included: the early break can cut live mask entries off), which the plan kernel computed
         tgt_p, msk_p = tgt_all[:max(rows, 1)], msk_all[:max(rows, 1)]
-        loss, nll = ops.masked_nll_fwd(logits[:rows].view(rows, 1, V1), tgt_p, msk_p, den=plan.den, lse=lse)
+        if smoothing > 0:
+            # the rows not given are the mask-0 tail and the reference's zero rows after its early break: a masked-in one of those adds
+            # m * H to the numerator, which the kernel takes from den - (mask sum of the rows given)
+            loss, nll = ops.smoothed_nll_fwd(logits[:rows].view(rows, 1, V1), tgt_p, msk_p, slp, smoothing, den=plan.den, lse=lse)
+        else:
+            loss, nll = ops.masked_nll_fwd(logits[:rows].view(rows, 1, V1), tgt_p, msk_p, den=plan.den, lse=lse)
 
         ctx.meta = (N, scale, S, T, T_live, R, E, A, V1, M, ot, rows)
-        ctx.masks = (k_xt, k_out)
+        ctx.masks, ctx.smoothing = (k_xt, k_out), smoothing
         ctx.flat_tokens = (tok_flat, k_flat)
         ctx.W, ctx.bf = W, bf
         ctx.pr, ctx.params, ctx.aux = pr, P, (plan, tokens_p, lens_p, tgt_p, msk_p, nll, lse)      # tokens_p: the words actually fed
@@ -230,7 +239,10 @@ class PackedDecoderLossFn(Function):
                 ops.copy2d(tmp, out_for(j).view(1, -1), accumulate=acc[j])
 
         dlogits = ops.empty_b16(max(rows, 1), V1, dev) if bf else new(max(rows, 1), V1)      # bf16: half the bytes of the largest tensor
-        ops.nll_logsoftmax_bwd(logp[:rows], tgt_p, msk_p, nll, dloss.contiguous(), dlogits[:rows], None, rows, 1, V1, lse=lse)
+        if ctx.smoothing > 0:
+            ops.smoothed_logsoftmax_bwd(logp[:rows], tgt_p, msk_p, nll, dloss.contiguous(), ctx.smoothing, dlogits[:rows], None, rows, 1, V1, lse=lse)
+        else:
+            ops.nll_logsoftmax_bwd(logp[:rows], tgt_p, msk_p, nll, dloss.contiguous(), dlogits[:rows], None, rows, 1, V1, lse=lse)
         wgrad(21, dlogits[:rows], Hout[:rows], bias=22)
         F_.grads_ready("logit")                                 # logit.* is final: its all-reduce overlaps the whole BPTT loop
         dHout = new(max(rows, 1), R); ops.gemm(dlogits[:rows], W[21], dHout[:rows])

@@ -698,10 +698,11 @@ class AttModel(CaptionModel):
 
     def _forward(self, fc_feats, att_feats, seq, att_masks=None, trip_pred=None, obj_dist=None, obj_box=None, rel_ind=None,
                  pred_fmap=None, pred_dist=None, gpn_obj_ind=None, gpn_pred_ind=None, gpn_nrel_ind=None, gpn_pool_mtx=None,
-                 fused_crit=None, need_outputs=True):
+                 fused_crit=None, need_outputs=True, label_smoothing=0.0):
         """`fused_crit=(target, mask)` (used by LossWrapper) also evaluates LanguageModelCriterion inside the
         decoder Function, so its backward never materialises the dense d(log-probs); the value is left in
-        `self.fused_lang_loss`.  The returned tuple is the reference's either way, except that with
+        `self.fused_lang_loss`.  `label_smoothing` > 0 beside it makes the fused criterion LabelSmoothing
+        (misc/utils.py:126-156) instead; 0 is the masked NLL with today's launches.  The returned tuple is the reference's either way, except that with
         `need_outputs=False` (LossWrapper only wants the loss) `outputs` is None and the decoder runs packed."""
         B, N, _ = att_feats.shape
         dev = att_feats.device
@@ -738,6 +739,8 @@ class AttModel(CaptionModel):
             sel_idx = c["ar_b5"]
             lens = ops.row_count(mask_sel)
         meta = {"N": N, "p": p, "masks": masks, "crit": fused_crit, "plan": plan, "tap": tap}
+        if fused_crit is not None and label_smoothing > 0:
+            meta["smoothing"] = ops.check_smoothing(label_smoothing)
         share = self.share_attention_sets == 1 or (self.share_attention_sets < 0 and p == 0.0)      # auto: only where it is exact
         if (not self.gpn and share and self.injected_masks is None and b5 % B == 0
                 and F_.shared_sets_ok(b5 // B, N, self.att_hid_size, R, T)):

@@ -10,7 +10,7 @@ import gc
 
 import torch
 
-from ._lib import SubgcError, call, lib
+from ._lib import SubgcError, call, call_criterion, lib
 
 RELU, ACCUM = 1, 2
 FLOPS = {"on": False, "gemm": 0.0, "gemm_bytes": 0.0, "gemm_calls": 0}
@@ -1398,6 +1398,51 @@ def masked_nll_bwd(target, mask, scratch, dloss, S, T, V):
 def nll_logsoftmax_bwd(logp, target, mask, scratch, dloss, dlogits, active, S, T, V, lse=None):
     call("subgc_nll_logsoftmax_bwd", _ptr(logp), _ptr(target, torch.int64), target.stride(0), _ptr(mask), mask.stride(0), _ptr(scratch),
          _ptr(dloss), _ptr(dlogits), ld(dlogits), S, T, V, _ptr(active, torch.int32), int(is_b16(dlogits)), _ptr(lse, torch.float32), _stream())
+    return dlogits
+
+
+# ---- label-smoothed language loss (include/subgc_criterion_hip.h; misc/utils.py:126-156)
+def check_smoothing(smoothing):
+    """-> float(smoothing); a value outside [0, 1] (NaN included) is refused here as the library refuses it, with the number in the text."""
+    s = float(smoothing)
+    if not 0.0 <= s <= 1.0:
+        raise SubgcError(f"label smoothing {s!r} is outside [0, 1]")
+    return s
+
+
+def row_lse_sum(x, raw=True):
+    """One read of x [rows, V] (subgc_row_lse_sum_f32).  raw: x holds logits -> (lse [rows], slp [rows] = sum_c (x - lse));
+    else x holds log-probabilities -> (None, slp = sum_c x)."""
+    rows, V = x.shape
+    lse = torch.empty(rows, device=x.device, dtype=torch.float32) if raw else None
+    slp = torch.empty(rows, device=x.device, dtype=torch.float32)
+    call_criterion("subgc_row_lse_sum_f32", _ptr(x, torch.float32), ld(x), rows, V, _ptr(lse), _ptr(slp), _stream())
+    return lse, slp
+
+
+def smoothed_nll_fwd(logp, target, mask, slp, smoothing, den=None, lse=None):
+    """LabelSmoothing's loss; arguments as masked_nll_fwd plus `slp` [S*T] (row_lse_sum) and `smoothing`.  `den`: the denominator over
+    rows not given, which are taken as the reference's zero rows.  -> (loss, scratch {num, den})."""
+    S, T, V = logp.shape
+    loss = torch.empty((), device=logp.device, dtype=torch.float32)
+    scratch = torch.empty(2, device=logp.device, dtype=torch.float32)
+    call_criterion("subgc_smoothed_nll_fwd", _ptr(logp, torch.float32), _ptr(target, torch.int64), target.stride(0), _ptr(mask, torch.float32),
+                   mask.stride(0), _ptr(slp, torch.float32), check_smoothing(smoothing), _ptr(loss), _ptr(scratch), S, T, V,
+                   _ptr(den, torch.float32), _ptr(lse, torch.float32), _stream())
+    return loss, scratch
+
+
+def smoothed_nll_bwd(target, mask, scratch, dloss, smoothing, S, T, V):
+    dlogp = torch.empty(S, T, V, device=mask.device, dtype=torch.float32)          # every element is written
+    call_criterion("subgc_smoothed_nll_bwd", _ptr(target, torch.int64), target.stride(0), _ptr(mask, torch.float32), mask.stride(0),
+                   _ptr(scratch), _ptr(dloss), check_smoothing(smoothing), _ptr(dlogp), S, T, V, _stream())
+    return dlogp
+
+
+def smoothed_logsoftmax_bwd(logp, target, mask, scratch, dloss, smoothing, dlogits, active, S, T, V, lse=None):
+    call_criterion("subgc_smoothed_logsoftmax_bwd", _ptr(logp, torch.float32), _ptr(target, torch.int64), target.stride(0), _ptr(mask, torch.float32),
+                   mask.stride(0), _ptr(scratch), _ptr(dloss), check_smoothing(smoothing), _ptr(dlogits), ld(dlogits), S, T, V,
+                   _ptr(active, torch.int32), int(is_b16(dlogits)), _ptr(lse, torch.float32), _stream())
     return dlogits
 
 
