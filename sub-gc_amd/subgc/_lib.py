@@ -26,6 +26,8 @@ GROUNDING_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "includ
 CONTROLLABILITY_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_controllability_hip.h")
 # the label-smoothed language loss (subgc_row_lse_sum_f32, subgc_smoothed_*): the fifth header, same arrangement
 CRITERION_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_criterion_hip.h")
+# self-critical training (subgc_sc_*, subgc_reward_*): the sixth header, same arrangement
+SELFCRITICAL_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_selfcritical_hip.h")
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -96,7 +98,8 @@ def lib():
         for hdr, protos in (("subgc_hip.h", _protos), ("subgc_metrics_hip.h", parse_header(METRICS_HEADER)),
                             ("subgc_grounding_hip.h", parse_header(GROUNDING_HEADER)),
                             ("subgc_controllability_hip.h", parse_header(CONTROLLABILITY_HEADER)),
-                            ("subgc_criterion_hip.h", parse_header(CRITERION_HEADER))):
+                            ("subgc_criterion_hip.h", parse_header(CRITERION_HEADER)),
+                            ("subgc_selfcritical_hip.h", parse_header(SELFCRITICAL_HEADER))):
             for name, (ret, args) in protos.items():
                 try:
                     fn = getattr(L, name)
@@ -138,7 +141,7 @@ def _call_in(header, cache, name, args):
         raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
 
 
-_FN_METRICS, _FN_GROUNDING, _FN_CONTROLLABILITY, _FN_CRITERION = {}, {}, {}, {}
+_FN_METRICS, _FN_GROUNDING, _FN_CONTROLLABILITY, _FN_CRITERION, _FN_SELFCRITICAL = {}, {}, {}, {}, {}
 
 
 def call_metrics(name, *args):
@@ -159,6 +162,11 @@ def call_controllability(name, *args):
 def call_criterion(name, *args):
     """`call` for the entry points of subgc_criterion_hip.h."""
     _call_in(CRITERION_HEADER, _FN_CRITERION, name, args)
+
+
+def call_selfcritical(name, *args):
+    """`call` for the entry points of subgc_selfcritical_hip.h."""
+    _call_in(SELFCRITICAL_HEADER, _FN_SELFCRITICAL, name, args)
 
 
 FAM = {"gemm": 1, "attn": 2, "lstm": 3, "gcn": 4, "pool": 5, "softmax": 6}

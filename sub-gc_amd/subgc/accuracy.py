@@ -144,8 +144,9 @@ class AccuracyScorer:
                 raise SubgcError(f"accuracy: batch image {i} names reference image {j}; the references hold {self.refs.n_img} images")
         return idx
 
-    def enqueue(self, seq, seg, I, d_index, first, remove_bad_endings, arena):
-        """The cook launch and the two accuracy launches on the current stream.  seq: device token rows [rows, T] (int32 / int64) in caption
+    def enqueue(self, seq, seg, I, d_index, first, remove_bad_endings, arena, oracle=True):
+        """The cook launch and the two accuracy launches on the current stream (`oracle=False`: the row records alone, without the per-image
+        launch -- the self-critical reward reads nothing else).  seq: device token rows [rows, T] (int32 / int64) in caption
         order; seg: device int32 row boundaries (>= I + 1 entries); d_index: device int32 [I], the reference image of every batch image;
         first: device int32 [I] image-local top-1 rows or None (row 0); arena: device int32 [arena_words(rows, I)], 8-byte aligned."""
         import torch
@@ -173,6 +174,8 @@ class AccuracyScorer:
                      P(rc, torch.int32), P(rl, torch.int32), P(rn, torch.float64), P(r.d_boff, torch.int32), P(r.d_bkeys, torch.int64),
                      P(r.d_bmax, torch.int32), len(r.bkeys), P(c.d_gauss, torch.float64), c.d_gauss.numel(), BETA2, P(row_i), ROW_INT,
                      P(row_d), ROW_F64, s)
+        if not oracle:
+            return
         call_metrics("subgc_accuracy_oracle", P(row_i), ROW_INT, P(row_d), ROW_F64, int(rows), P(seg, torch.int32), int(I), self.oracle_num,
                      P(first, torch.int32), P(img_i), IMG_INT, P(img_d), IMG_F64, s)
 

@@ -647,6 +647,31 @@ class SmoothedNLLFn(Function):
         return ops.smoothed_nll_bwd(target, mask, scratch, dloss.contiguous(), ctx.smoothing, S, T, V), None, None, None
 
 
+class RewardNLLFn(Function):
+    """RewardCriterion (misc/utils.py:89-109): (input [S,T] gathered log-probs, seq, reward, gpn_loss [S] or None) -> loss; gradients go
+    to `input` and to `gpn_loss` when given, `reward` is data as in the reference."""
+
+    @staticmethod
+    def forward(ctx, inp, seq, reward, gpn_loss):
+        inp, seq, reward = inp.contiguous(), seq.contiguous(), reward.contiguous()
+        if inp.dim() != 2 or seq.shape != inp.shape or reward.shape != inp.shape:
+            raise ops.SubgcError(f"RewardCriterion: input, seq and reward are [S, T]; got {tuple(inp.shape)}, {tuple(seq.shape)}, {tuple(reward.shape)}")
+        if gpn_loss is not None:
+            gpn_loss = gpn_loss.contiguous()
+            if gpn_loss.shape != inp.shape[:1]:
+                raise ops.SubgcError(f"RewardCriterion: gpn_loss is [S] = [{inp.size(0)}]; got {tuple(gpn_loss.shape)}")
+        loss, scratch = ops.reward_nll_fwd(inp, seq, reward, gpn_loss)
+        ctx.save_for_backward(seq, reward, scratch)
+        ctx.gpn = gpn_loss
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        seq, reward, scratch = ctx.saved_tensors
+        dinput, dgpn = ops.reward_nll_bwd(seq, reward, ctx.gpn, scratch, dloss.contiguous())
+        return dinput, None, None, dgpn
+
+
 # ------------------------------------------------------------------------------- decoder
 DIRECT_GRADS = True               # accumulate parameter gradients straight into existing .grad buffers
 DEFER_DU = True                   # per-sentence attention sets: d(u) formed once after the BPTT loop (subgc_attn_du_accum) instead of read-modify-written per step
@@ -1016,7 +1041,10 @@ class DecoderFn(Function):
                        step_logp=logits3.permute(1, 0, 2).clone(), fed_tokens=tokens[:, :T].t().clone())
         crit = meta.get("crit")                      # (target [S,T] view, mask [S,T] view): criterion fused in
         smoothing = meta.get("smoothing", 0.0)       # > 0: LabelSmoothing (misc/utils.py:126-156) in the place of LanguageModelCriterion
-        if crit is not None and smoothing > 0:
+        reward = meta.get("reward") if crit is not None else None      # [S,T] view: RewardCriterion (misc/utils.py:89-109) in that place
+        if reward is not None:
+            loss, nll_scratch = ops.reward_logits_fwd(logits.view(S, T, V1), crit[0], crit[1], reward)
+        elif crit is not None and smoothing > 0:
             # rows after the early break are zero rows (`active`): lp = 0, so a masked-in one adds m * H, as in the reference
             _, slp = ops.row_lse_sum(logits, raw=False)
             loss, nll_scratch = ops.smoothed_nll_fwd(logits.view(S, T, V1), crit[0], crit[1], slp, smoothing)
@@ -1027,7 +1055,7 @@ class DecoderFn(Function):
         ctx.meta = (N, scale, S, T, R, E, A, V1)
         ctx.masks = (k_xt, k_out)
         ctx.pr = pr
-        ctx.crit, ctx.smoothing = crit, smoothing
+        ctx.crit, ctx.smoothing, ctx.reward = crit, smoothing, reward
         ctx.nll_scratch = nll_scratch
         ctx.params, ctx.W, ctx.bf = P, W, bf
         ctx.set_materialize_grads(False)
@@ -1084,7 +1112,10 @@ class DecoderFn(Function):
             for j in (i, also):
                 ops.copy2d(tmp, out_for(j).view(1, -1), accumulate=acc[j])
 
-        def crit_bwd(dst_):                               # d(logits) of the fused criterion: NLL, or its smoothed twin
+        def crit_bwd(dst_):                               # d(logits) of the fused criterion: NLL, its smoothed or its reward-weighted twin
+            if ctx.reward is not None:
+                return ops.reward_logsoftmax_bwd(logp, ctx.crit[0], ctx.crit[1], ctx.reward, ctx.nll_scratch, dloss.contiguous(), dst_, active,
+                                                 S, T, V1)
             if ctx.smoothing > 0:
                 return ops.smoothed_logsoftmax_bwd(logp, ctx.crit[0], ctx.crit[1], ctx.nll_scratch, dloss.contiguous(), ctx.smoothing, dst_, active,
                                                    S, T, V1)

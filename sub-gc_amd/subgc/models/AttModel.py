@@ -138,6 +138,8 @@ class AttModel(CaptionModel):
         self.dropout_seed = g("seed", 2019)
         self._dropout_calls = 0
         self.injected_masks = None       # tests inject {'fc','att','xt','out','gpn_hid'} keep-masks here
+        self.injected_sc = None          # tests inject the rollout tokens [2 * b5, T] of a self-critical step (sampled half first)
+        self.sc_stats = None             # left by a self-critical step: {"reward": mean reward (device scalar), "seq": rollout tokens}
         self.injected_ss = None          # tests inject (selector uniforms [T,S], draw uniforms [T,S]) for scheduled sampling
         # debug tap (tests only): set to a dict and the next `model(...)` / `_sample` call files its intermediates there under the
         # oracle's / golden files' names (fusion_x, gcn_x_layer{l}, x_obj_out, read_out, att_sel, fc_sel, p_fc, p_att, pp_att,
@@ -698,18 +700,30 @@ class AttModel(CaptionModel):
 
     def _forward(self, fc_feats, att_feats, seq, att_masks=None, trip_pred=None, obj_dist=None, obj_box=None, rel_ind=None,
                  pred_fmap=None, pred_dist=None, gpn_obj_ind=None, gpn_pred_ind=None, gpn_nrel_ind=None, gpn_pool_mtx=None,
-                 fused_crit=None, need_outputs=True, label_smoothing=0.0):
+                 fused_crit=None, need_outputs=True, label_smoothing=0.0, self_critical=None):
         """`fused_crit=(target, mask)` (used by LossWrapper) also evaluates LanguageModelCriterion inside the
         decoder Function, so its backward never materialises the dense d(log-probs); the value is left in
         `self.fused_lang_loss`.  `label_smoothing` > 0 beside it makes the fused criterion LabelSmoothing
         (misc/utils.py:126-156) instead; 0 is the masked NLL with today's launches.  The returned tuple is the reference's either way, except that with
-        `need_outputs=False` (LossWrapper only wants the loss) `outputs` is None and the decoder runs packed."""
+        `need_outputs=False` (LossWrapper only wants the loss) `outputs` is None and the decoder runs packed.
+        `self_critical=(SelfCriticalReward, device int32 image indices)` makes the step a self-critical one (subgc/selfcritical.py): after
+        the encoder and the sGPN, which run once as always, a rollout on the detached `fc` / node states samples a caption and its greedy
+        baseline per sub-graph, the reward is scored on the device, and the decoder Function replays the sampled tokens (`seq` then only
+        gives the batch's shape) with RewardCriterion (misc/utils.py:89-109) fused in its place: `self.fused_lang_loss` is the reward
+        loss, `self.sc_stats = {"reward": mean reward, "seq": the rollout's tokens}`.  The decoder's four dropout masks have p = 0 and
+        scheduled sampling is off in such a step, so the policy that is differentiated is the policy that sampled; `label_smoothing`
+        does not apply.  `self.injected_sc` [2 * b5, T] replaces the rollout's tokens (test plumbing, like `injected_ss`)."""
         B, N, _ = att_feats.shape
         dev = att_feats.device
         self.__dict__.pop("_grads_are_zero", None)      # a backward may follow: "the optimizer left the gradient buffer zeroed" ends here
         L, R, E = self.GCN_dim, self.rnn_size, self.input_encoding_size
         b5, T = seq.size(0), seq.size(1) - 1
         p = self.drop_prob_lm if self.training else 0.0
+        if self_critical is not None:
+            # the rollout is as long as the loader's captions (labels are [0, caption, 0]) and the replay's labels are [0, sampled row, 0]:
+            # the same T steps as a cross-entropy step; no decoder dropout
+            T_roll, p, label_smoothing = T - 1, 0.0, 0.0
+            fused_crit = ()                                                               # (target, mask) follow the rollout
         hb = gpn_obj_ind.size(2) if gpn_obj_ind is not None else 1
         # the packed decoder's plan kernels keep a sentence's live steps in a 64-bit mask and the sentence order in LDS (csrc/plan.hip:
         # T <= 63, S <= 16384); longer captions / larger shards run the unpacked DecoderFn (same kernels, every step of every sentence)
@@ -717,7 +731,7 @@ class AttModel(CaptionModel):
         packed = (fused_crit is not None and not need_outputs and self.packed_decoder and self.injected_masks is None and tap is None
                   and T <= F_.PACKED_MAX_STEPS and b5 <= F_.PACKED_MAX_SENTENCES)
         plan = None
-        if packed:                                                                        # the packed decoder's row plan, read behind an event
+        if packed and self_critical is None:                                              # the packed decoder's row plan, read behind an event
             from ..functions_packed import PlanAhead
             plan = PlanAhead(seq.contiguous(), fused_crit[1])
         masks = self._masks({"fc": ((b5, R), p), "att": ((b5 * N, R), p), "xt": ((T, b5, E), p), "out": ((T, b5, R), p),
@@ -738,7 +752,26 @@ class AttModel(CaptionModel):
             ops.fill2d_(mask_sel[:, :36], 1.0)                                            # in place on the caller's tensor
             sel_idx = c["ar_b5"]
             lens = ops.row_count(mask_sel)
+        reward = None
+        if self_critical is not None:
+            from .. import selfcritical
+            scorer, d_index = self_critical
+            seq2 = self.injected_sc
+            if seq2 is None:
+                seq2 = selfcritical.rollout(self, fc, Xb, lens, sel_idx, img_s, N, T=T_roll)
+            elif tuple(seq2.shape) != (2 * b5, T_roll):
+                raise ops.SubgcError(f"injected_sc: rollout tokens [2 * b5, T] = [{2 * b5}, {T_roll}], got {tuple(seq2.shape)}")
+            # one launch: the replay's labels and RewardCriterion's mask (misc/utils.py:98-99) and the rows the reward scores
+            seq, crit_mask, rows = ops.sc_prepare(seq2.contiguous(), self.vocab_size + 1, scorer.refs.eos_id)
+            reward, mean_reward, _ = scorer.enqueue(seq2, d_index, rows=rows)
+            fused_crit = (seq[:, 1:], crit_mask)
+            self.sc_stats = {"reward": mean_reward, "seq": seq2}
+            if packed:
+                from ..functions_packed import PlanAhead
+                plan = PlanAhead(seq, crit_mask)                                          # the plan sees the 0/1 mask, never the reward
         meta = {"N": N, "p": p, "masks": masks, "crit": fused_crit, "plan": plan, "tap": tap}
+        if reward is not None:
+            meta["reward"] = reward
         if fused_crit is not None and label_smoothing > 0:
             meta["smoothing"] = ops.check_smoothing(label_smoothing)
         share = self.share_attention_sets == 1 or (self.share_attention_sets < 0 and p == 0.0)      # auto: only where it is exact
@@ -752,7 +785,7 @@ class AttModel(CaptionModel):
         if self.bf16_storage:
             flat16 = self.weights_b16()
             meta["W16"] = [self.W16(n, flat16) for n in F_.PARAM_ORDER]
-        ss_on = self.training and self.ss_prob > 0.0
+        ss_on = self.training and self.ss_prob > 0.0 and self_critical is None            # upstream applies ss_prob in `forward` mode only
         if ss_on:                                                                         # scheduled sampling, AttModel.py:157-167
             if self.injected_ss is not None:
                 sel_u, u = self.injected_ss

@@ -9,7 +9,7 @@ import torch
 
 from .AttModel import AttModel, TopDownModel  # noqa: F401
 from .CaptionModel import CaptionModel  # noqa: F401
-from .loss_wrapper import LabelSmoothing, LanguageModelCriterion, LossWrapper  # noqa: F401
+from .loss_wrapper import LabelSmoothing, LanguageModelCriterion, LossWrapper, RewardCriterion  # noqa: F401
 
 
 def optimistic_restore(network, state_dict, word_map_path="data/word_mapping.npy"):

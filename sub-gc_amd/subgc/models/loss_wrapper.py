@@ -34,9 +34,19 @@ class LabelSmoothing(torch.nn.Module):
         return F_.SmoothedNLLFn.apply(input, target, mask, self.smoothing)
 
 
+class RewardCriterion(torch.nn.Module):
+    """misc/utils.py:89-109, the reference's signature: `input` [S, T] the log-probabilities gathered at `seq`, `reward` [S, T] (any per-token
+    reward), `gpn_loss` [S] optional.  Runs as subgc_reward_nll_fwd / _bwd (include/subgc_selfcritical_hip.h); `reward` gets no gradient."""
+
+    def forward(self, input, seq, reward, gpn_loss=None):
+        return F_.RewardNLLFn.apply(input, seq, reward, gpn_loss)
+
+
 class LossWrapper(torch.nn.Module):
-    def __init__(self, model, opt):
+    def __init__(self, model, opt, sc_reward=None):
+        """`sc_reward`: a subgc.selfcritical.SelfCriticalReward; with it `forward(..., sc_flag=True)` is a self-critical step."""
         super().__init__()
+        self.sc_reward = sc_reward
         self.opt = opt
         self.model = model
         # `opt` may be None (the benchmark and the tools) or lack the attribute: LanguageModelCriterion, every launch as before
@@ -47,7 +57,13 @@ class LossWrapper(torch.nn.Module):
             self.crit = LanguageModelCriterion()
 
     def forward(self, fc_feats, att_feats, labels, masks, att_masks, gts, gt_indices, trip_pred, obj_dist, obj_box, rel_ind,
-                pred_fmap, pred_dist, gpn_obj_ind, gpn_pred_ind, gpn_nrel_ind, gpn_pool_mtx):
+                pred_fmap, pred_dist, gpn_obj_ind, gpn_pred_ind, gpn_nrel_ind, gpn_pool_mtx, sc_flag=False):
+        """`sc_flag` (the upstream name): a self-critical step -- the language loss is RewardCriterion on a rollout of the model's own,
+        `gt_indices` are the images' positions in the RewardReferences, `gts` is not read, `label_smoothing` does not apply, and the
+        result carries the mean reward as well.  False or absent: every launch as before."""
+        if sc_flag:
+            return self._forward_sc(fc_feats, att_feats, labels, att_masks, gt_indices, trip_pred, obj_dist, obj_box, rel_ind, pred_fmap,
+                                    pred_dist, gpn_obj_ind, gpn_pred_ind, gpn_nrel_ind, gpn_pool_mtx)
         T = labels.size(1) - 1
         fused = (labels[:, 1:], masks[:, 1:T + 1]) if getattr(self.model, "supports_fused_crit", False) else None
         kw = {"fused_crit": fused, "need_outputs": False} if fused is not None else {}
@@ -61,3 +77,20 @@ class LossWrapper(torch.nn.Module):
         else:
             lang_loss = self.crit(lang_output, labels[:, 1:], masks[:, 1:]) if lang_output is not None else None
         return {"gpn_loss": gpn_loss, "lang_loss": lang_loss}
+
+    def _forward_sc(self, fc_feats, att_feats, labels, att_masks, gt_indices, trip_pred, obj_dist, obj_box, rel_ind, pred_fmap, pred_dist,
+                    gpn_obj_ind, gpn_pred_ind, gpn_nrel_ind, gpn_pool_mtx):
+        if self.sc_reward is None:
+            raise ops.SubgcError("LossWrapper: sc_flag=True needs a reward: build subgc.selfcritical.RewardReferences from the training captions "
+                                 "and pass LossWrapper(model, opt, sc_reward=subgc.selfcritical.SelfCriticalReward(refs, cider_weight, bleu_weight))")
+        if not getattr(self.model, "supports_fused_crit", False):
+            raise ops.SubgcError("LossWrapper: a self-critical step needs a model whose _forward takes `self_critical` (AttModel)")
+        if torch.is_tensor(gt_indices) and gt_indices.is_cuda:
+            d_index = gt_indices.to(torch.int32)             # already on the device: debug bounds mode checks it (subgc_accuracy_rows)
+        else:
+            idx = self.sc_reward.check_index(gt_indices.tolist() if torch.is_tensor(gt_indices) else gt_indices)
+            d_index = ops.upload(idx, torch.int32, att_feats.device)
+        _, gpn_loss, _ = self.model(fc_feats, att_feats, labels, att_masks, trip_pred, obj_dist, obj_box, rel_ind, pred_fmap, pred_dist,
+                                    gpn_obj_ind, gpn_pred_ind, gpn_nrel_ind, gpn_pool_mtx, need_outputs=False,
+                                    self_critical=(self.sc_reward, d_index))
+        return {"gpn_loss": gpn_loss, "lang_loss": self.model.fused_lang_loss, "reward": self.model.sc_stats["reward"]}

@@ -7,10 +7,11 @@ here (see functions.py) and no fallback: CPU tensors raise.
 from __future__ import annotations
 
 import gc
+import math
 
 import torch
 
-from ._lib import SubgcError, call, call_criterion, lib
+from ._lib import SubgcError, call, call_criterion, call_selfcritical, lib
 
 RELU, ACCUM = 1, 2
 FLOPS = {"on": False, "gemm": 0.0, "gemm_bytes": 0.0, "gemm_calls": 0}
@@ -1443,6 +1444,87 @@ def smoothed_logsoftmax_bwd(logp, target, mask, scratch, dloss, smoothing, dlogi
     call_criterion("subgc_smoothed_logsoftmax_bwd", _ptr(logp, torch.float32), _ptr(target, torch.int64), target.stride(0), _ptr(mask, torch.float32),
                    mask.stride(0), _ptr(scratch), _ptr(dloss), check_smoothing(smoothing), _ptr(dlogits), ld(dlogits), S, T, V,
                    _ptr(active, torch.int32), int(is_b16(dlogits)), _ptr(lse, torch.float32), _stream())
+    return dlogits
+
+
+# ---- self-critical sequence training (include/subgc_selfcritical_hip.h; misc/utils.py:89-109)
+def check_reward_weights(cider_weight, bleu_weight):
+    """-> (float, float); a weight that is not finite is refused here as the library refuses it, with the numbers in the text."""
+    wc, wb = float(cider_weight), float(bleu_weight)
+    if not (math.isfinite(wc) and math.isfinite(wb)):
+        raise SubgcError(f"self-critical reward: the reward weights (cider {wc!r}, bleu {wb!r}) must be finite")
+    return wc, wb
+
+
+def sc_pick(logits, n_sample, temp, u, t, seq, seqlp, next_tok, unfinished, n_unf, prev_count=None, raw=False):
+    """One rollout step (subgc_sc_pick): rows [0, n_sample) draw from softmax(logits / temp) with u[r], the others take the first arg-max
+    exactly as decode_pick(k = 0) does; the bookkeeping is decode_pick's."""
+    n, V = logits.shape
+    call_selfcritical("subgc_sc_pick", _ptr(logits, torch.float32), ld(logits), n, int(n_sample), V, float(temp), _ptr(u, torch.float32), int(t),
+                      _ptr(seq, torch.int64), _ptr(seqlp, torch.float32), seq.size(1), _ptr(next_tok, torch.int64),
+                      _ptr(unfinished, torch.int32), _ptr(n_unf, torch.int32), _ptr(prev_count, torch.int32), int(raw), _stream())
+
+
+def sc_prepare(seq2, V, eos_id=0, want_replay=True, want_rows=True):
+    """Rollout tokens seq2 [2S, T] int64 (sampled half first) -> (labels [S, T+2], mask [S, T+1], score_rows [2S, T+1]) in one launch
+    (subgc_sc_prepare); an output not wanted is None."""
+    if seq2.dim() != 2 or seq2.size(0) % 2 or seq2.size(0) == 0 or not seq2.is_contiguous():
+        raise SubgcError(f"sc_prepare: contiguous rollout tokens [2 S, T], got {tuple(seq2.shape)}")
+    S, T = seq2.size(0) // 2, seq2.size(1)
+    dev = seq2.device
+    labels = torch.empty(S, T + 2, device=dev, dtype=torch.int64) if want_replay else None
+    mask = torch.empty(S, T + 1, device=dev, dtype=torch.float32) if want_replay else None
+    rows = torch.empty(2 * S, T + 1, device=dev, dtype=torch.int64) if want_rows else None
+    call_selfcritical("subgc_sc_prepare", _ptr(seq2, torch.int64), S, T, int(V), int(eos_id), _ptr(labels), _ptr(mask), _ptr(rows), _stream())
+    return labels, mask, rows
+
+
+def sc_reward(row_d, S, T1, cider_weight, bleu_weight):
+    """fp64 row records of subgc_accuracy_rows for 2S rows -> (reward [S, T1] fp32, mean_reward [] fp32, scores [2S] fp64)."""
+    wc, wb = check_reward_weights(cider_weight, bleu_weight)
+    dev = row_d.device
+    reward = torch.empty(S, T1, device=dev, dtype=torch.float32)
+    mean = torch.empty((), device=dev, dtype=torch.float32)
+    scores = torch.empty(2 * S, device=dev, dtype=torch.float64)
+    call_selfcritical("subgc_sc_reward", _ptr(row_d, torch.float64), ld(row_d), int(S), int(T1), wc, wb, _ptr(reward), _ptr(mean), _ptr(scores),
+                      _stream())
+    return reward, mean, scores
+
+
+def reward_nll_fwd(inp, seq, reward, gpn_loss=None):
+    """RewardCriterion.forward on gathered log-probabilities [S, T] (all contiguous) -> (loss, scratch {num, den})."""
+    S, T = inp.shape
+    loss = torch.empty((), device=inp.device, dtype=torch.float32)
+    scratch = torch.empty(2, device=inp.device, dtype=torch.float32)
+    call_selfcritical("subgc_reward_nll_fwd", _ptr(inp, torch.float32), _ptr(seq, torch.int64), _ptr(reward, torch.float32),
+                      _ptr(gpn_loss, torch.float32), _ptr(loss), _ptr(scratch), S, T, _stream())
+    return loss, scratch
+
+
+def reward_nll_bwd(seq, reward, gpn_loss, scratch, dloss):
+    S, T = seq.shape
+    dinput = torch.empty(S, T, device=seq.device, dtype=torch.float32)           # every element is written
+    dgpn = torch.empty(S, device=seq.device, dtype=torch.float32) if gpn_loss is not None else None
+    call_selfcritical("subgc_reward_nll_bwd", _ptr(seq, torch.int64), _ptr(reward, torch.float32), _ptr(gpn_loss, torch.float32), _ptr(scratch),
+                      _ptr(dloss), _ptr(dinput), _ptr(dgpn), S, T, _stream())
+    return dinput, dgpn
+
+
+def reward_logits_fwd(logp, target, mask, reward, den=None, lse=None):
+    """RewardCriterion fused on the decoder's rows: masked_nll_fwd's arguments plus `reward` ([S, T] view) -> (loss, scratch {num, den})."""
+    S, T, V = logp.shape
+    loss = torch.empty((), device=logp.device, dtype=torch.float32)
+    scratch = torch.empty(2, device=logp.device, dtype=torch.float32)
+    call_selfcritical("subgc_reward_logits_fwd", _ptr(logp, torch.float32), _ptr(target, torch.int64), target.stride(0), _ptr(mask, torch.float32),
+                      mask.stride(0), _ptr(reward, torch.float32), reward.stride(0), _ptr(loss), _ptr(scratch), S, T, V,
+                      _ptr(den, torch.float32), _ptr(lse, torch.float32), _stream())
+    return loss, scratch
+
+
+def reward_logsoftmax_bwd(logp, target, mask, reward, scratch, dloss, dlogits, active, S, T, V, lse=None):
+    call_selfcritical("subgc_reward_logsoftmax_bwd", _ptr(logp, torch.float32), _ptr(target, torch.int64), target.stride(0),
+                      _ptr(mask, torch.float32), mask.stride(0), _ptr(reward, torch.float32), reward.stride(0), _ptr(scratch), _ptr(dloss),
+                      _ptr(dlogits), ld(dlogits), S, T, V, _ptr(active, torch.int32), int(is_b16(dlogits)), _ptr(lse, torch.float32), _stream())
     return dlogits
 
 
