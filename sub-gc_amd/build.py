@@ -36,6 +36,7 @@ def build(force=False, verbose=True):
     hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_controllability_hip.h"))
     hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_criterion_hip.h"))
     hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_selfcritical_hip.h"))
+    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_consensus_hip.h"))
     jobs = []
     for s in srcs:
         src, obj = os.path.join(CSRC, s), os.path.join(OBJ, s[:-4] + ".o")

@@ -1,8 +1,8 @@
 // What the metric kernels (consensus, diversity, accuracy, grounding, controllability) agree on, written once: how a token row becomes a
 // caption, how its n-grams become 64-bit keys, and the CIDEr / BLEU pieces that more than one family spells.  Device functions only, all
-// inlined.  NO floating-point contraction pragma here: accuracy.hip, grounding.hip and controllability.hip turn contraction off for the
-// whole file and include this header AFTER that pragma, consensus.hip and diversity.hip keep the compiler's default -- every file gets
-// these functions under its own setting.
+// inlined.  NO floating-point contraction pragma here: accuracy.hip, grounding.hip, controllability.hip and consensus_bleu.hip turn
+// contraction off for the whole file and include this header AFTER that pragma, consensus.hip and diversity.hip keep the compiler's
+// default -- every file gets these functions under its own setting.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -91,6 +91,62 @@ __device__ __forceinline__ void cider_finish(double (&v)[4], const double (&hn)[
         if (hn[k] != 0.0 && rn[k] != 0.0) v[k] /= hn[k] * rn[k];
 #pragma unroll
     for (int k = 0; k < 4; ++k) v[k] *= g;
+}
+
+// What the two consensus methods (consensus.hip: 'cider', consensus_bleu.hip: 'bleu') do around their pair score, for a workgroup of 256
+// that every thread enters.  The captions of image i's first k neighbour images, listed in neighbour order (consensus_reranking.py:
+// 155-157): caps[0 .. count) = corpus caption indices, at most max_caps of them; pre: k + 1 ints of scratch.  -> count.  A neighbour
+// index out of range is clamped (debug bounds mode reports it instead).  The caller synchronises before it reads caps.
+__device__ __forceinline__ int neighbour_captions(const int32_t* __restrict__ nn, int nn_ld, int i, int k, const int32_t* __restrict__ cap_off,
+                                                  int n_img, int max_caps, int32_t* pre, int32_t* caps, int t) {
+    int b0 = 0, bn = 0;
+    if (t < k) {
+        int img = nn[(int64_t)i * nn_ld + t];
+        img = img < 0 ? 0 : (img >= n_img ? n_img - 1 : img);
+        b0 = cap_off[img];
+        bn = cap_off[img + 1] - b0;
+        if (bn < 0) bn = 0;
+        pre[t + 1] = bn;
+    }
+    if (t == 0) pre[0] = 0;
+    __syncthreads();
+    if (t == 0)
+        for (int q = 1; q <= k; ++q) pre[q] += pre[q - 1];
+    __syncthreads();
+    if (t < k) {
+        const int p = pre[t];
+        for (int q = 0; q < bn && p + q < max_caps; ++q) caps[p + q] = b0 + q;
+    }
+    return pre[k] < max_caps ? pre[k] : max_caps;
+}
+// The pair scores sc[0 .. nc) (all >= 0; sc holds the next power of two) sorted descending in place, then the first min(m, nc) added in
+// that order by thread 0, as `b_s_arr.sort(reverse=True); sum(b_s_arr[:m])` does (:168-169) -> the sum (thread 0 only).  Additions
+// only: nothing here can contract.
+__device__ __forceinline__ double sum_top_desc(double* sc, int nc, int m, int t) {
+    int n2 = 1;
+    while (n2 < nc) n2 <<= 1;
+    for (int j = nc + t; j < n2; j += 256) sc[j] = -1.0;                   // below every score
+    __syncthreads();
+    for (int size = 2; size <= n2; size <<= 1) {                            // bitonic, descending
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int q = t; q < n2; q += 256) {
+                const int p = q ^ stride;
+                if (p > q) {
+                    const double x = sc[q], y = sc[p];
+                    const bool down = (q & size) == 0;
+                    if (down ? x < y : x > y) { sc[q] = y; sc[p] = x; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    double acc = 0.0;
+    if (t == 0) {
+        const int mm = m < nc ? m : nc;
+#pragma unroll 8
+        for (int q = 0; q < mm; ++q) acc += sc[q];
+    }
+    return acc;
 }
 
 // BLEU's "closest" reference length (bleu_scorer.py:76-77 `min((abs(l - testlen), l) for l in reflen)[1]`): over len[0 .. n) without

@@ -134,25 +134,7 @@ __global__ __launch_bounds__(256) void score_kernel(const uint64_t* __restrict__
         hk[q] = ckeys[(int64_t)row * cstride + q];
         hw[q] = cw[(int64_t)row * cstride + q];
     }
-    int b0 = 0, bn = 0;
-    if (t < k) {
-        int img = nn[(int64_t)i * nn_ld + t];
-        img = img < 0 ? 0 : (img >= n_img ? n_img - 1 : img);              // debug bounds mode reports these instead
-        b0 = cap_off[img];
-        bn = cap_off[img + 1] - b0;
-        if (bn < 0) bn = 0;
-        pre[t + 1] = bn;
-    }
-    if (t == 0) pre[0] = 0;
-    __syncthreads();
-    if (t == 0)
-        for (int q = 1; q <= k; ++q) pre[q] += pre[q - 1];
-    __syncthreads();
-    if (t < k) {
-        const int p = pre[t];
-        for (int q = 0; q < bn && p + q < max_caps; ++q) caps[p + q] = b0 + q;
-    }
-    const int nc = pre[k] < max_caps ? pre[k] : max_caps;
+    const int nc = neighbour_captions(nn, nn_ld, i, k, cap_off, n_img, max_caps, pre, caps, t);
     const double hn[4] = {cnorm[(int64_t)row * 4], cnorm[(int64_t)row * 4 + 1], cnorm[(int64_t)row * 4 + 2], cnorm[(int64_t)row * 4 + 3]};
     const int hl = clen[row];
     __syncthreads();
@@ -170,30 +152,8 @@ __global__ __launch_bounds__(256) void score_kernel(const uint64_t* __restrict__
         sc[j] = score;
         if (pair_out) pair_out[(int64_t)row * pair_ld + j] = score;
     }
-    int n2 = 1;
-    while (n2 < nc) n2 <<= 1;
-    for (int j = nc + t; j < n2; j += 256) sc[j] = -1.0;                   // below every score (all are >= 0)
-    __syncthreads();
-    for (int size = 2; size <= n2; size <<= 1) {                            // bitonic, descending
-        for (int stride = size >> 1; stride > 0; stride >>= 1) {
-            for (int q = t; q < n2; q += 256) {
-                const int p = q ^ stride;
-                if (p > q) {
-                    const double x = sc[q], y = sc[p];
-                    const bool down = (q & size) == 0;
-                    if (down ? x < y : x > y) { sc[q] = y; sc[p] = x; }
-                }
-            }
-            __syncthreads();
-        }
-    }
-    if (t == 0) {
-        const int mm = m < nc ? m : nc;
-        double acc = 0.0;
-#pragma unroll 8
-        for (int q = 0; q < mm; ++q) acc += sc[q];
-        sim[row] = acc;
-    }
+    const double acc = sum_top_desc(sc, nc, m, t);
+    if (t == 0) sim[row] = acc;
 }
 
 // One workgroup per image: order[seg[i] + r] = the image-local index of its r-th best candidate by the fp64 sums, descending, equal sums

@@ -28,6 +28,8 @@ CONTROLLABILITY_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "
 CRITERION_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_criterion_hip.h")
 # self-critical training (subgc_sc_*, subgc_reward_*): the sixth header, same arrangement
 SELFCRITICAL_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_selfcritical_hip.h")
+# consensus re-ranking, method 'bleu' (subgc_consensus_bleu_*): the seventh header, same arrangement
+CONSENSUS_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_consensus_hip.h")
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -99,7 +101,8 @@ def lib():
                             ("subgc_grounding_hip.h", parse_header(GROUNDING_HEADER)),
                             ("subgc_controllability_hip.h", parse_header(CONTROLLABILITY_HEADER)),
                             ("subgc_criterion_hip.h", parse_header(CRITERION_HEADER)),
-                            ("subgc_selfcritical_hip.h", parse_header(SELFCRITICAL_HEADER))):
+                            ("subgc_selfcritical_hip.h", parse_header(SELFCRITICAL_HEADER)),
+                            ("subgc_consensus_hip.h", parse_header(CONSENSUS_HEADER))):
             for name, (ret, args) in protos.items():
                 try:
                     fn = getattr(L, name)
@@ -141,7 +144,7 @@ def _call_in(header, cache, name, args):
         raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
 
 
-_FN_METRICS, _FN_GROUNDING, _FN_CONTROLLABILITY, _FN_CRITERION, _FN_SELFCRITICAL = {}, {}, {}, {}, {}
+_FN_METRICS, _FN_GROUNDING, _FN_CONTROLLABILITY, _FN_CRITERION, _FN_SELFCRITICAL, _FN_CONSENSUS = {}, {}, {}, {}, {}, {}
 
 
 def call_metrics(name, *args):
@@ -167,6 +170,11 @@ def call_criterion(name, *args):
 def call_selfcritical(name, *args):
     """`call` for the entry points of subgc_selfcritical_hip.h."""
     _call_in(SELFCRITICAL_HEADER, _FN_SELFCRITICAL, name, args)
+
+
+def call_consensus(name, *args):
+    """`call` for the entry points of subgc_consensus_hip.h."""
+    _call_in(CONSENSUS_HEADER, _FN_CONSENSUS, name, args)
 
 
 FAM = {"gemm": 1, "attn": 2, "lstm": 3, "gcn": 4, "pool": 5, "softmax": 6}

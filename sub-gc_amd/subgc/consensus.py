@@ -1,18 +1,21 @@
-"""Consensus re-ranking, method 'cider', of a whole decode batch on the device
-(misc/consensus_reranking/cr_mRNN_demo.py -> concensus_reranking_utils/consensus_reranking.py:122-179; the pair score is
-CiderScorer.compute_cider_sen_pair, external/coco_caption_patch_mRNN_cr/cider_scorer_compute_sentence.py:187-264).
+"""Consensus re-ranking, methods 'cider' and 'bleu', of a whole decode batch on the device
+(misc/consensus_reranking/cr_mRNN_demo.py -> concensus_reranking_utils/consensus_reranking.py:122-179; the pair scores are
+CiderScorer.compute_cider_sen_pair, external/coco_caption_patch_mRNN_cr/cider_scorer_compute_sentence.py:187-264, and
+calculate_bleu_sentence, concensus_reranking_utils/bleu_score_util.py:15-61).
 
-The reference re-ranks each image's candidate captions by the sum of their `m` largest CIDEr similarities to the captions of the image's
+The reference re-ranks each image's candidate captions by the sum of their `m` largest similarities to the captions of the image's
 `k` nearest training images -- a triple Python loop over string-keyed dictionaries, run on the captions `eval_split` wrote.  Here words
-become 16-bit ids once on the host, an n-gram is one 64-bit key, and three launches (`subgc_consensus_cook / _score / _rank`) take the
-decode loop's token rows to a per-image order.  `ConsensusCorpus` is the one-time setup (numpy / torch allowed); `ConsensusReranker.rerank`
-and the `consensus=` argument of `eval_glue.caption_images` are the per-batch path and issue only C-ABI launches.
+become 16-bit ids once on the host, an n-gram is one 64-bit key, and three launches (`subgc_consensus_cook / _score / _rank`, or
+`subgc_consensus_bleu_cook / _bleu_score` and the same `_rank`) take the decode loop's token rows to a per-image order.
+`ConsensusCorpus` is the one-time setup (numpy / torch allowed); `ConsensusReranker.rerank` / `BleuConsensusReranker.rerank` and the
+`consensus=` argument of `eval_glue.caption_images` are the per-batch path and issue only C-ABI launches.  `make_reranker` picks the
+class and the reference's defaults (conf_cr.py:43-48) by method name.
 
 Tie rule: `np.argsort(-sim)` leaves the order of equal sums unspecified, and duplicate captions from different sub-graphs make exact
 ties routine.  The device order is STABLE: among equal sums the lower candidate index comes first.
 
 Out of scope: the nearest-image search (`find_NNimg`, a float64 cdist over ResNet features that are not shipped) -- the caller supplies
-the neighbour index lists the reference caches as `NNimg_list_*.npy`; `method='bleu'`; PTB tokenisation and the COCO metric scripts.
+the neighbour index lists the reference caches as `NNimg_list_*.npy`; PTB tokenisation and the COCO metric scripts.
 """
 from __future__ import annotations
 
@@ -128,6 +131,7 @@ class ConsensusCorpus:
                 bad[int(k)] = 1
         self.bad = bad
         self.device = None
+        self._bleu_cooked = None
         if device == "auto":
             device = torch.device("cuda", torch.cuda.current_device())
         if device is not None:
@@ -144,8 +148,18 @@ class ConsensusCorpus:
         self.d_gauss = torch.from_numpy(self.gauss).to(dev)
         self.d_bad = torch.from_numpy(self.bad).to(dev)
         self.cooked = ops.consensus_cook(self.d_words, self.d_ukeys, self.d_ulogdf, self.ref_len, woff=self.d_woff, max_words=self.max_words)
+        self._bleu_cooked = None
         self.device = dev
         return self
+
+    def bleu_cooked(self):
+        """Every corpus caption's n-gram key / count list for method 'bleu' (`subgc_consensus_bleu_cook`): one launch on first use, over
+        the words and offsets `to` uploaded, then cached; the 'cider' tables are not touched."""
+        if self.device is None:
+            raise SubgcError("consensus: the corpus is not on a device (ConsensusCorpus(..., device=...) or .to(device))")
+        if self._bleu_cooked is None:
+            self._bleu_cooked = ops.consensus_bleu_cook(self.d_words, woff=self.d_woff, max_words=self.max_words)
+        return self._bleu_cooked
 
     def encode(self, words):
         """A caption (list of words, or a string) -> ids; words the corpus never saw and the model does not know get id 0 -> refused."""
@@ -197,11 +211,16 @@ class ConsensusReranker:
             raise SubgcError("consensus: top_k >= 1 or None")
         nn, max_caps = self.neighbours(nn_lists)
         d_nn = torch.from_numpy(nn).to(seq.device)
+        self._score(seq, T, seg, I, max_rows, top_k, d_nn, max_caps, remove_bad_endings, sim, pair_out)
+        ops.consensus_rank(sim, seg, I, top_k, order, first)
+        return max_caps
+
+    def _score(self, seq, T, seg, I, max_rows, top_k, d_nn, max_caps, remove_bad_endings, sim, pair_out):
+        """The method's two launches: cook the candidate rows, score them against the neighbour captions."""
+        c = self.corpus
         cand = ops.consensus_cook(seq, c.d_ukeys, c.d_ulogdf, c.ref_len, bad=c.d_bad if remove_bad_endings else None)
         ops.consensus_score(cand, T, seg, I, max_rows, top_k, d_nn, self.k, c.d_cap_off, c.n_img, c.n_caps, c.d_woff, c.cooked, c.d_gauss,
                             self.m, max_caps, sim, pair_out)
-        ops.consensus_rank(sim, seg, I, top_k, order, first)
-        return max_caps
 
     def rerank(self, seq, bounds, nn_lists, top_k=None, remove_bad_endings=0, return_pairs=False):
         """seq [rows, T]: the decode batch's device token rows, image i owning rows bounds[i] .. bounds[i+1]-1 in sGPN-ranked order;
@@ -235,6 +254,100 @@ class ConsensusReranker:
             hp = pairs.cpu().numpy()
             return out_o, out_s, [hp[a:a + n] for a, n in zip(bounds, keep)]
         return out_o, out_s
+
+
+class BleuConsensusReranker(ConsensusReranker):
+    """`consensus_rerank(method='bleu')` for a decode batch: as ConsensusReranker -- same `neighbours`, `enqueue`, `rerank` and returns,
+    so it serves as `consensus={"reranker": ...}` of `ops.eval_collect` / `eval_glue.caption_images` -- with the m-RNN sentence-level
+    n-gram F-score (bleu_score_util.py:15-61) as the pair score: `subgc_consensus_bleu_cook / _bleu_score` of
+    include/subgc_consensus_hip.h.  Defaults k_bleu = 60, m_bleu = 175, bleu_ngram = 4, fpr_bleu = 1.0 (conf_cr.py:45-48).  The corpus
+    cooks its n-gram count lists on the first enqueue."""
+
+    def __init__(self, corpus, k=60, m=175, ngram=4, fpr=1.0):
+        super().__init__(corpus, k=k, m=m)
+        if isinstance(ngram, bool) or int(ngram) != ngram or not 1 <= ngram <= 4:
+            raise SubgcError(f"consensus: ngram = {ngram}; n-gram orders 1 .. 4")
+        fpr = float(fpr)
+        if not np.isfinite(fpr) or fpr < 0.0:
+            raise SubgcError(f"consensus: fpr = {fpr}; a finite weight >= 0")
+        self.ngram, self.fpr = int(ngram), fpr
+
+    def _score(self, seq, T, seg, I, max_rows, top_k, d_nn, max_caps, remove_bad_endings, sim, pair_out):
+        c = self.corpus
+        cand = ops.consensus_bleu_cook(seq, bad=c.d_bad if remove_bad_endings else None)
+        ops.consensus_bleu_score(cand, T, seg, I, max_rows, top_k, d_nn, self.k, c.d_cap_off, c.n_img, c.n_caps, c.d_woff, c.bleu_cooked(),
+                                 self.ngram, self.fpr, self.m, max_caps, sim, pair_out)
+
+
+def make_reranker(corpus, method="cider", **kw):
+    """`consensus_rerank(method=...)` (consensus_reranking.py:122-143): the re-ranker of the method with the reference's defaults
+    (conf_cr.py:43-48: cider k = 60, m = 125; bleu k = 60, m = 175, ngram = 4, fpr = 1.0); keywords override them."""
+    if method == "cider":
+        return ConsensusReranker(corpus, **kw)
+    if method == "bleu":
+        return BleuConsensusReranker(corpus, **kw)
+    raise SubgcError(f"consensus: method = {method!r}; only support cider and bleu currently")      # consensus_reranking.py:123-124
+
+
+def _ngram_counters(ids):
+    """Per order 1 .. 4 the dictionary n-gram (id tuple) -> count: `Counter(ngrams(sentence, o))`."""
+    out = []
+    for o in range(1, 5):
+        d = {}
+        for p in range(len(ids) - o + 1):
+            g = tuple(ids[p:p + o])
+            d[g] = d.get(g, 0) + 1
+        out.append(d)
+    return out
+
+
+def _bleu_pair(tc, tl, rc, rl, n, fpr):
+    if n > tl or n > rl:                                                     # bleu_score_util.py:27: n, not the order at hand
+        return 0.0
+    total = 0.0
+    for o in range(n):
+        acc = 0
+        small, big = (tc[o], rc[o]) if len(tc[o]) <= len(rc[o]) else (rc[o], tc[o])
+        for g, x in small.items():
+            y = big.get(g)
+            if y is not None:
+                acc += min(x, y)
+        f = 0.0
+        if acc != 0:
+            pre = float(acc) / float(tl - o)
+            rec = float(acc) / float(rl - o)
+            f = ((fpr + 1) * pre * rec) / (rec + fpr * pre)
+        total = total + f                                                    # left to right, where the reference calls math.fsum
+    return total / float(n)
+
+
+def bleu_pair_restatement(t_ids, r_ids, n, fpr):
+    """The device contract of one pair score (include/subgc_consensus_hip.h), restated with Python floats (IEEE fp64, one rounding per
+    operation): calculate_bleu_sentence of bleu_score_util.py:15-61 on word ids, with the plain left-to-right sum of the n F-scores in
+    place of math.fsum.  t_ids: the candidate's ids, r_ids: the neighbour caption's."""
+    t_ids, r_ids = [int(x) for x in t_ids], [int(x) for x in r_ids]
+    return _bleu_pair(_ngram_counters(t_ids), len(t_ids), _ngram_counters(r_ids), len(r_ids), int(n), float(fpr))
+
+
+def bleu_rerank_restatement(cands, ref_ids, nn, k, m, n, fpr):
+    """One image of consensus_reranking.py:152-172 with that pair score: candidates (id lists) against the captions (`ref_ids`: per
+    corpus image a list of id lists) of its first k neighbours -> (pair scores [candidates, captions], sums of the m largest added in
+    descending order as Python's sum adds the sorted list, the stable descending order of the sums: lower index first among equals)."""
+    caps = []
+    for j in range(k):
+        caps += ref_ids[int(nn[j])]
+    rc = [(_ngram_counters(r), len(r)) for r in caps]
+    pairs = np.zeros((len(cands), len(caps)))
+    sums = np.zeros(len(cands))
+    seen = {}
+    for a, c in enumerate(cands):
+        key = tuple(int(x) for x in c)
+        if key not in seen:                                                  # duplicate candidates are scored once
+            tc = _ngram_counters(list(key))
+            seen[key] = [_bleu_pair(tc, len(key), r, rl, int(n), float(fpr)) for r, rl in rc]
+        pairs[a] = seen[key]
+        sums[a] = sum(sorted(seen[key], reverse=True)[:m])
+    return pairs, sums, np.argsort(-sums, kind="stable")
 
 
 def save_rerank_ind(path, rerank_ind):

@@ -81,7 +81,8 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
     position and the full-graph node id (= box row) it stands for (grd_utils.py:36-47; `grounding_material` finishes the entry).
 
     `consensus={"reranker": ConsensusReranker, "nn": {image_id: [nearest training-image indices]}, "top_k": 4}` (default None: off)
-    re-ranks every image's sGPN-sorted captions -- its best `top_k`, None = all -- by CIDEr consensus on the device, in the decode
+    re-ranks every image's sGPN-sorted captions -- its best `top_k`, None = all -- by CIDEr consensus (or, with a
+    `BleuConsensusReranker`, by the m-RNN sentence BLEU: `consensus.make_reranker(corpus, method)`) on the device, in the decode
     batch's own pass (subgc.consensus; cr_mRNN_demo.py -> consensus_rerank).  Every entry gains `"consensus_rerank_ind"` (indices into
     its `caption` list, best first, equal sums in ascending index: what the reference's consensus_rerank_ind.npy holds) and
     `"consensus_sim"` (the fp64 sums of those captions).  With `return_att` the grounding entry is the re-ranker's FIRST choice, picked on

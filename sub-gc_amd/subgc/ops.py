@@ -11,7 +11,7 @@ import math
 
 import torch
 
-from ._lib import SubgcError, call, call_criterion, call_selfcritical, lib
+from ._lib import SubgcError, call, call_consensus, call_criterion, call_selfcritical, lib
 
 RELU, ACCUM = 1, 2
 FLOPS = {"on": False, "gemm": 0.0, "gemm_bytes": 0.0, "gemm_calls": 0}
@@ -1770,6 +1770,43 @@ def consensus_rank(sim, seg, I, top_k, order, first=None):
     call("subgc_consensus_rank", _ptr(sim, torch.float64), _ptr(seg, torch.int32), int(I), int(top_k), _ptr(order, torch.int32),
          _ptr(first, torch.int32), _stream())
     return order
+
+
+def consensus_bleu_cook(tok, woff=None, max_words=0, row_len=None, bad=None):
+    """subgc_consensus_bleu_cook (include/subgc_consensus_hip.h): sentences -> their distinct n-grams of orders 1 .. 4 in ascending key
+    order with an int32 count each (the Counters of bleu_score_util.py:33-34, all orders at once).  tok and the sentence arguments are
+    consensus_cook's.  -> (keys int64 bit patterns, counts int32, cnt int32 [S], wlen int32 [S]: the words of each sentence); sentence s
+    owns keys / counts [4 * first word ...)."""
+    p_tok = _ptr(tok)
+    if tok.dtype not in (torch.int32, torch.int64) or not tok.is_contiguous():
+        raise SubgcError(f"consensus_bleu_cook: contiguous int32 / int64 tokens, got {tok.dtype}")
+    if woff is not None:
+        S, T = woff.numel() - 1, 0
+    else:
+        S, T = tok.shape
+    dev = tok.device
+    keys = torch.empty(max(4 * tok.numel(), 1), device=dev, dtype=torch.int64)
+    counts = torch.empty(max(4 * tok.numel(), 1), device=dev, dtype=torch.int32)
+    cnt = torch.empty(max(S, 1), device=dev, dtype=torch.int32)
+    wlen = torch.empty(max(S, 1), device=dev, dtype=torch.int32)
+    call_consensus("subgc_consensus_bleu_cook", p_tok, int(tok.dtype == torch.int64), _ptr(woff, torch.int32), int(T), _ptr(row_len, torch.int32),
+                   _ptr(bad, torch.uint8), 0 if bad is None else bad.numel(), int(S), int(max_words), _ptr(keys), _ptr(counts), _ptr(cnt),
+                   _ptr(wlen), _stream())
+    return keys, counts, cnt, wlen
+
+
+def consensus_bleu_score(cand, T, seg, I, max_cand, top_k, nn, k, cap_off, n_img, n_caps, nwoff, corpus, n, fpr, m, max_caps, sim, pair_out=None):
+    """subgc_consensus_bleu_score: sim[row] = sum of the m largest sentence-level BLEU F-scores (bleu_score_util.py:15-61) of candidate
+    `row` against its image's neighbour captions (consensus_reranking.py:155-169).  cand / corpus: the tuples consensus_bleu_cook
+    returned (rows of width T / CSR over nwoff); nn int32 [I, >= k]; n the n-gram order, fpr the F-score's precision weight."""
+    ck, cc, cn, cl = cand
+    nk, nc, nn_, nl = corpus
+    call_consensus("subgc_consensus_bleu_score", _ptr(ck, torch.int64), _ptr(cc, torch.int32), _ptr(cn, torch.int32), _ptr(cl, torch.int32), int(T),
+                   _ptr(seg, torch.int32), int(I), int(max_cand), int(top_k), _ptr(nn, torch.int32), nn.stride(0) if nn.dim() == 2 else nn.numel(),
+                   int(k), _ptr(cap_off, torch.int32), int(n_img), int(n_caps), _ptr(nwoff, torch.int32), _ptr(nk, torch.int64),
+                   _ptr(nc, torch.int32), _ptr(nn_, torch.int32), _ptr(nl, torch.int32), int(n), float(fpr), int(m), int(max_caps),
+                   _ptr(sim, torch.float64), _ptr(pair_out, torch.float64), 0 if pair_out is None else pair_out.stride(0), _stream())
+    return sim
 
 
 DIV_COLS = 8            # SUBGC_DIV_SEL: the integer columns in front of a set's selection (drawn, distinct, selected, words, unigrams, bigrams, novel, valid)
