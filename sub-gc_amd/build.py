@@ -37,6 +37,7 @@ def build(force=False, verbose=True):
     hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_criterion_hip.h"))
     hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_selfcritical_hip.h"))
     hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_consensus_hip.h"))
+    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_forced_hip.h"))
     jobs = []
     for s in srcs:
         src, obj = os.path.join(CSRC, s), os.path.join(OBJ, s[:-4] + ".o")

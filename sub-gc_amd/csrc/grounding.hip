@@ -11,6 +11,7 @@
 #pragma clang fp contract(off)
 
 #include "caption.h"      // after the pragma: its functions are compiled without contraction here
+#include "grounding_iou.h" // the IoU, shared with grounding_gt.hip
 
 namespace {
 
@@ -58,24 +59,6 @@ __global__ __launch_bounds__(64) void material_kernel(const void* __restrict__ t
     mat_box[o * 4 + 3] = bx.w;
 }
 
-// bbox_overlaps_batch for one predicted box p and one ground-truth box g (bbox_transform.py:194-220), every operation rounded on its own
-__device__ __forceinline__ float iou(const float4 p, const float4 g) {
-    const float gx = (g.z - g.x) + 1.f, gy = (g.w - g.y) + 1.f;
-    const float ga = gx * gy;
-    const float px = (p.z - p.x) + 1.f, py = (p.w - p.y) + 1.f;
-    const float pa = px * py;
-    float iw = (fminf(p.z, g.z) - fmaxf(p.x, g.x)) + 1.f;
-    iw = iw < 0.f ? 0.f : iw;
-    float ih = (fminf(p.w, g.w) - fmaxf(p.y, g.y)) + 1.f;
-    ih = ih < 0.f ? 0.f : ih;
-    const float inter = iw * ih;
-    const float ua = (pa + ga) - inter;
-    float ov = __fdiv_rn(inter, ua);
-    if (gx == 1.f && gy == 1.f) ov = 0.f;
-    if (px == 1.f && py == 1.f) ov = -1.f;
-    return ov;
-}
-
 // One wave per (batch image, reference caption) pair.
 __global__ __launch_bounds__(64) void score_kernel(const int32_t* __restrict__ mat_n, const int32_t* __restrict__ mat_cls, const float* __restrict__ mat_box,
                                                    int ld_m, int I, const int32_t* __restrict__ img_ref, int n_ref, const int32_t* __restrict__ pair_off,
@@ -120,7 +103,7 @@ __global__ __launch_bounds__(64) void score_kernel(const int32_t* __restrict__ m
             if (best >= 0) {
                 const float* pb = mat_box + (mb + lane) * 4;
                 const float* gb = obj_box + (int64_t)(q0 + best) * 4;
-                const float ov = iou(make_float4(pb[0], pb[1], pb[2], pb[3]), make_float4(gb[0], gb[1], gb[2], gb[3]));
+                const float ov = subgc_grounding_iou(make_float4(pb[0], pb[1], pb[2], pb[3]), make_float4(gb[0], gb[1], gb[2], gb[3]));
                 code = ov > iou_thresh ? SUBGC_GRD_HIT : SUBGC_GRD_MISS;
             } else {
                 const int lem = class_lemma[clampi(cls, 0, n_class - 1)];
@@ -147,7 +130,7 @@ __global__ __launch_bounds__(64) void score_kernel(const int32_t* __restrict__ m
             if (first >= 0) {
                 const float* pb = mat_box + (mb + first) * 4;
                 const float* gb = obj_box + (int64_t)(q0 + lane) * 4;
-                const float ov = iou(make_float4(pb[0], pb[1], pb[2], pb[3]), make_float4(gb[0], gb[1], gb[2], gb[3]));
+                const float ov = subgc_grounding_iou(make_float4(pb[0], pb[1], pb[2], pb[3]), make_float4(gb[0], gb[1], gb[2], gb[3]));
                 code = ov > iou_thresh ? SUBGC_GRD_HIT : SUBGC_GRD_MISS;
             }
         } else {

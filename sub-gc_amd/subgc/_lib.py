@@ -30,6 +30,8 @@ CRITERION_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "includ
 SELFCRITICAL_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_selfcritical_hip.h")
 # consensus re-ranking, method 'bleu' (subgc_consensus_bleu_*): the seventh header, same arrangement
 CONSENSUS_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_consensus_hip.h")
+# forced decode and grounding on ground-truth sentences (subgc_forced_*, subgc_gt_grounding_*): the eighth header, same arrangement
+FORCED_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_forced_hip.h")
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -102,7 +104,8 @@ def lib():
                             ("subgc_controllability_hip.h", parse_header(CONTROLLABILITY_HEADER)),
                             ("subgc_criterion_hip.h", parse_header(CRITERION_HEADER)),
                             ("subgc_selfcritical_hip.h", parse_header(SELFCRITICAL_HEADER)),
-                            ("subgc_consensus_hip.h", parse_header(CONSENSUS_HEADER))):
+                            ("subgc_consensus_hip.h", parse_header(CONSENSUS_HEADER)),
+                            ("subgc_forced_hip.h", parse_header(FORCED_HEADER))):
             for name, (ret, args) in protos.items():
                 try:
                     fn = getattr(L, name)
@@ -145,6 +148,7 @@ def _call_in(header, cache, name, args):
 
 
 _FN_METRICS, _FN_GROUNDING, _FN_CONTROLLABILITY, _FN_CRITERION, _FN_SELFCRITICAL, _FN_CONSENSUS = {}, {}, {}, {}, {}, {}
+_FN_FORCED = {}
 
 
 def call_metrics(name, *args):
@@ -175,6 +179,11 @@ def call_selfcritical(name, *args):
 def call_consensus(name, *args):
     """`call` for the entry points of subgc_consensus_hip.h."""
     _call_in(CONSENSUS_HEADER, _FN_CONSENSUS, name, args)
+
+
+def call_forced(name, *args):
+    """`call` for the entry points of subgc_forced_hip.h."""
+    _call_in(FORCED_HEADER, _FN_FORCED, name, args)
 
 
 FAM = {"gemm": 1, "attn": 2, "lstm": 3, "gcn": 4, "pool": 5, "softmax": 6}

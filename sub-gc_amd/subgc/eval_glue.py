@@ -335,3 +335,73 @@ def grounding_material(entry, boxes, wd_to_lemma, lemma_det_id_dict, det_id_to_d
             out["clss"].append(det_id_to_det_wd[lemma_det_id_dict[lemma]])
             out["idx_in_sent"].append(j)
     return out
+
+
+@torch.no_grad()
+def ground_gt_images(model, images, infos, gt, group=64):
+    """Grounding on GROUND-TRUTH sentences (misc/grounding/eval_grd_flickr30k_entities.py:63-109, the evaluator's `--eval_mode GT`) for a
+    list of loader items: every reference caption of an image is decoded teacher-forced on the sub-graph the caller pairs it with --
+    candidate j of the image carries caption j (the loaders' entries 0-4 are the sentences' own sub-graphs; a Full-GC model repeats the
+    full graph) -- and the word at every annotated `process_idx` is grounded to the node it attended to most.
+    gt = {"scorer": GtGroundingScorer, "index": {image_id: index of the image in the scorer's references}, "rows": GtCaptionRows or
+    {image_id: int token rows [captions, Tf]}, "boxes": {image_id: the detector's boxes [N, 4]}, "img_wh": {image_id: (w, h)} or None
+    (boxes used as given; else rescaled like grd_utils.py:27)}.
+    Per batch of `group` images: one forced decode (subgc.forced), `subgc_grounding_argmax` with one row per "image",
+    `subgc_gt_grounding_material`, `subgc_gt_grounding_score`, and ONE host copy.  -> one entry per image: {"image_id", "gt_grounding":
+    `GtGroundingScorer.unpack`'s entry (the {'idx_in_sent','bbox'} list of every caption and one event code per annotated object),
+    "caption_ll": {"ll" fp64, "n_tok" int32, "perplexity" fp64} per caption}; `grounding_gt.summarize` of the "gt_grounding" entries gives
+    grd_accu, `grounding_gt.to_submission` the dict the reference evaluator reads.  Not sharded."""
+    from . import forced
+    from ._lib import SubgcError, call
+    from .grounding import prepare_boxes
+    scorer, wh = gt["scorer"], gt.get("img_wh")
+    if len(infos) != len(images):
+        raise ValueError("ground_gt_images: one `infos` entry per image")
+    missing = [info["id"] for info in infos if info["id"] not in gt["index"] or info["id"] not in gt["boxes"]]
+    if missing:
+        raise ValueError(f"ground_gt_images: gt['index'] / ['boxes'] name no reference image or no boxes for image ids {missing[:5]}")
+    scorer._need_device()
+    out = []
+    for i0 in range(0, len(images), max(1, int(group))):
+        chunk, ids = images[i0:i0 + group], [info["id"] for info in infos[i0:i0 + group]]
+        tokens = [np.asarray(gt["rows"][k]) for k in ids]
+        plan = scorer.plan([gt["index"][k] for k in ids], [len(t) for t in tokens])
+        boxes = [prepare_boxes(gt["boxes"][k], None if wh is None else wh[k]) for k in ids]
+        hold = forced.forced_decode(model, chunk, tokens, return_att=True)
+        rows, I = hold["rows"], len(chunk)
+        if rows == 0:
+            for k, e in zip(ids, scorer.unpack(np.zeros(scorer.arena_words(plan), np.int32), plan)):
+                out.append({"image_id": k, "gt_grounding": e, "caption_ll": {"ll": np.zeros(0), "n_tok": np.zeros(0, np.int32), "perplexity": np.zeros(0)}})
+            continue
+        Tf, dev, bounds = hold["Tf"], hold["seq"].device, hold["bounds"]
+        n_box = sum(len(b) for b in boxes)
+        row_img = np.repeat(np.arange(I), np.diff(bounds))
+        box_off = np.concatenate([[0], np.cumsum([len(b) for b in boxes])])
+        n_t = len(plan["table"])
+        tables = ops.upload(np.concatenate([plan["table"], row_img, box_off, np.arange(rows + 1)]).astype(np.int32), torch.int32, dev)
+        seg = tables[n_t + rows + I + 1:]
+        d_box = ops.upload(np.concatenate(boxes).ravel() if n_box else np.zeros(4, np.float32), torch.float32, dev)
+        # one int32 arena: ll (fp64) | n_tok | att2 | node | n_words | the scorer's lists and codes
+        g_words = scorer.arena_words(plan)
+        arena = torch.empty(3 * rows + 2 * rows * Tf + rows + g_words, device=dev, dtype=torch.int32)
+        o = 2 * rows
+        ll = arena[:o].view(torch.float64)
+        n_tok = arena[o:o + rows]; o += rows
+        att2 = arena[o:o + rows * Tf]; o += rows * Tf
+        node = arena[o:o + rows * Tf]; o += rows * Tf
+        nw = arena[o:o + rows]; o += rows
+        ops.copy_(ll, hold["ll"]); ops.copy_(n_tok, hold["n_tok"])
+        AL, idx = hold["AL"], hold["idx"]
+        if AL.stride(2) != 1 or idx.stride(1) != 1:
+            raise SubgcError("ground_gt_images: AL / idx need unit inner strides")
+        call("subgc_grounding_argmax", ops._ptr(AL, torch.float32), AL.stride(0), AL.stride(1), AL.size(2), Tf, ops._ptr(hold["seq"], torch.int64), Tf,
+             ops._ptr(idx, torch.int64), idx.stride(0), ops._ptr(seg, torch.int32), None, None, rows, ops._ptr(att2), ops._ptr(node), ops._ptr(nw),
+             ops._stream())
+        scorer.enqueue(node, Tf, nw, tables, I, d_box, n_box, arena[o:o + g_words], plan)
+        host = arena.cpu().numpy()                                        # the one copy (synchronises the stream)
+        h_ll, h_tok = host[:2 * rows].view(np.float64).copy(), host[2 * rows:3 * rows].copy()
+        entries = scorer.unpack(host[o:o + g_words], plan)
+        for k, e, a, b in zip(ids, entries, bounds, bounds[1:]):
+            out.append({"image_id": k, "gt_grounding": e,
+                        "caption_ll": {"ll": h_ll[a:b], "n_tok": h_tok[a:b], "perplexity": forced.perplexity(h_ll[a:b], h_tok[a:b])}})
+    return out

@@ -14,7 +14,8 @@ it is asked for reference tokens and class words only, at cook time, never per b
 `grounding=` argument of `eval_glue.caption_images` are the per-batch path and issue only C-ABI launches; `score_submission` is the drop-in
 for grounding_score.py on a finished `grounding_file.json`.
 
-Out of scope: `gt_grd_eval` (boxes on ground-truth sentences) and CoreNLP itself (the controllability scores: subgc.controllability).
+`gt_grd_eval` (grounding accuracy on ground-truth sentences, the evaluator's default mode) is subgc.grounding_gt: a forced decode plus
+its own score kernel on these same reference tables.  Out of scope: CoreNLP itself (the controllability scores: subgc.controllability).
 """
 from __future__ import annotations
 
