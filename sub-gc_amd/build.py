@@ -30,14 +30,8 @@ def build(force=False, verbose=True):
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_hip.h"))
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_metrics_hip.h"))
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_grounding_hip.h"))
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_controllability_hip.h"))
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_criterion_hip.h"))
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_selfcritical_hip.h"))
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_consensus_hip.h"))
-    hdrs.append(os.path.join(os.path.dirname(HERE), "include", "subgc_forced_hip.h"))
+    inc = os.path.join(os.path.dirname(HERE), "include")
+    hdrs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]
     jobs = []
     for s in srcs:
         src, obj = os.path.join(CSRC, s), os.path.join(OBJ, s[:-4] + ".o")

@@ -5,26 +5,11 @@
 // directly from the raw logits (the log-softmax of AttModel.py:340 is folded in), so a step hands the
 // host 2*k numbers per row instead of a normalised and sorted vocabulary row.
 #include "common.h"
+#include "rowwise.h"
 
 namespace {
 
 constexpr int TOPK_MAX = 32;
-
-__device__ __forceinline__ void argmax_merge(float& v, int& i, float* sv, int* si) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(i, o, 64);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { sv[w] = v; si[w] = i; }
-    __syncthreads();
-    v = sv[0]; i = si[0];
-    for (int k = 1; k < nw; ++k)
-        if (sv[k] > v || (sv[k] == v && si[k] < i)) { v = sv[k]; i = si[k]; }
-}
 
 // Order: value descending, then index ascending (a total order, so "everything after the previous
 // pick" is a single comparison and the k passes need no list of used indices).
@@ -37,23 +22,9 @@ __global__ __launch_bounds__(256) void row_topk_kernel(const float* __restrict__
     const int r = blockIdx.x;
     const float* p = x + (int64_t)r * ld;
     float reg[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int c = threadIdx.x + j * 256;
-        reg[j] = c < cols ? p[c] : -INFINITY;
-    }
+    row_load<PER>(p, cols, reg);
     float lse = 0.f;
-    if (normalise) {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) mx = fmaxf(mx, reg[j]);
-        mx = block_max(mx, smf);
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) sum += (threadIdx.x + j * 256 < cols) ? expf(reg[j] - mx) : 0.f;
-        sum = block_sum(sum, smf);
-        lse = mx + logf(sum);
-    }
+    if (normalise) lse = row_lse<PER>(reg, cols, smf, RowPlain{});
     float pv = INFINITY; int pi = -1;
     for (int q = 0; q < k; ++q) {
         float bv = -INFINITY; int bi = 0x7fffffff;
@@ -64,7 +35,7 @@ __global__ __launch_bounds__(256) void row_topk_kernel(const float* __restrict__
             const bool after = v < pv || (v == pv && c > pi);
             if (c < cols && after && (v > bv || bi == 0x7fffffff)) { bv = v; bi = c; }
         }
-        argmax_merge(bv, bi, sv, si);
+        block_argmax(bv, bi, sv, si);
         if (threadIdx.x == 0) {
             vals[(int64_t)r * k + q] = bv - lse;
             idx[(int64_t)r * k + q] = bi;
@@ -103,11 +74,7 @@ __global__ __launch_bounds__(256) void row_topk_merge_kernel(const float* __rest
     const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const float* p = x + (int64_t)r * ld;
     float reg[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int c = threadIdx.x + j * 256;
-        reg[j] = c < cols ? p[c] : -INFINITY;
-    }
+    row_load<PER>(p, cols, reg);
     float tv[K]; int ti[K];
 #pragma unroll
     for (int q = 0; q < K; ++q) { tv[q] = -INFINITY; ti[q] = 0x7fffffff; }
@@ -142,12 +109,8 @@ __global__ __launch_bounds__(256) void row_topk_merge_kernel(const float* __rest
     }
     float lse = 0.f;
     if (normalise) {
-        const float mx = tv[0];
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) sum += (threadIdx.x + j * 256 < cols) ? expf(reg[j] - mx) : 0.f;
-        sum = block_sum(sum, smf);
-        lse = mx + logf(sum);
+        const float mx = tv[0];                                            // the first winner is the row maximum
+        lse = mx + logf(row_sum_exp<PER>(reg, cols, mx, smf, RowPlain{}));
     }
     if (threadIdx.x == 0) {
 #pragma unroll
@@ -167,17 +130,12 @@ SUBGC_API int subgc_row_topk_f32(const float* x, int64_t ld, int rows, int cols,
     const int per = (cols + 255) / 256;
     if (k <= 4 && per <= 40) {                                             // beam 2 (test.sh, Sub_GC_Kar): beam + 2 = 4 leading columns
 #define LAUNCHM(P) hipLaunchKernelGGL((row_topk_merge_kernel<P, 4>), dim3(rows), dim3(256), 0, (hipStream_t)stream, x, ld, cols, k, log_softmax, vals, idx)
-        if (per <= 4) LAUNCHM(4);
-        else if (per <= 16) LAUNCHM(16);
-        else LAUNCHM(40);
+        SUBGC_DISPATCH_PER(per, LAUNCHM);                                  // (per <= 40 here: the 64 arm is never taken)
 #undef LAUNCHM
         return subgc::check_launch("subgc_row_topk_f32");
     }
 #define LAUNCH(P) hipLaunchKernelGGL(row_topk_kernel<P>, dim3(rows), dim3(256), 0, (hipStream_t)stream, x, ld, cols, k, log_softmax, vals, idx)
-    if (per <= 4) LAUNCH(4);
-    else if (per <= 16) LAUNCH(16);
-    else if (per <= 40) LAUNCH(40);
-    else LAUNCH(64);
+    SUBGC_DISPATCH_PER(per, LAUNCH);
 #undef LAUNCH
     return subgc::check_launch("subgc_row_topk_f32");
 }

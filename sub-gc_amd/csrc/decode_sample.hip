@@ -21,6 +21,7 @@
 //             does not depend on the levels before it, so the result equals the one-launch form bit for bit.
 // No float atomics, nothing depends on scheduling: equal inputs give equal bits.  No synchronisation, no allocation: capturable.
 #include "common.h"
+#include "rowwise.h"
 
 #include <climits>
 
@@ -34,37 +35,6 @@ __device__ __forceinline__ uint32_t order_key(float x) {         // a < b  <=>  
 __device__ __forceinline__ float key_value(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 __device__ __forceinline__ unsigned long long composite(float x, int c) {
     return ((unsigned long long)order_key(x) << 16) | (unsigned long long)(0xFFFF - c);
-}
-// inclusive scan over the 256 threads in thread order; sm: >= 4 ints
-__device__ __forceinline__ int block_scan_incl(int v, int* sm) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    __syncthreads();
-    if (lane == 63) sm[w] = v;
-    __syncthreads();
-    for (int i = 0; i < w; ++i) v += sm[i];
-    return v;
-}
-// exclusive scan over the 256 threads in thread order (a fixed tree per wave, the wave totals added in wave order); sm: >= 4 floats
-__device__ __forceinline__ float block_scan_excl(float v, float* sm) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    float exc = __shfl_up(v, 1, 64);
-    if (lane == 0) exc = 0.f;
-    __syncthreads();
-    if (lane == 63) sm[w] = v;
-    __syncthreads();
-    float base = 0.f;
-    for (int i = 0; i < w; ++i) base += sm[i];
-    return base + exc;
 }
 
 // One 256-thread workgroup per row; the row (<= 256*PER logits) is loaded into registers once, like decode_pick_kernel<PER>.
@@ -87,12 +57,9 @@ __global__ __launch_bounds__(256) void decode_sample_kernel(const float* __restr
     const int tid = threadIdx.x, r = blockIdx.x;
     const float* p = logits + (int64_t)r * ld;
     float x[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int c = tid + j * 256;
-        x[j] = c < V ? p[c] : -INFINITY;
-    }
-    // v = log_softmax(x / temp) = x / temp - lse (the additions of decode_pick_kernel)
+    row_load<PER>(p, V, x);
+    // v = log_softmax(x / temp) = x / temp - lse; the registers keep the raw logits (the radix select orders those).  row_lse with
+    // RowTempered spelled out: through the helper this kernel's launches measured 1-3 % slower (profiles/r18_row_refactor_ab.txt)
     float mx = -INFINITY;
 #pragma unroll
     for (int j = 0; j < PER; ++j) mx = fmaxf(mx, x[j] / temp);
@@ -232,13 +199,7 @@ __global__ __launch_bounds__(256) void decode_sample_kernel(const float* __restr
         const unsigned long long e = buf[min(s_pick, m - 1)];
         const int it = 0xFFFF - (int)(e & 0xFFFFull);
         const float lp = key_value((uint32_t)(e >> 16)) / temp - lse;    // un-renormalised: the reference gathers from the scattered row
-        int unf = (t == 0) ? (it > 0) : (unfinished[r] && it > 0);
-        unfinished[r] = unf;
-        const int64_t w = unf ? it : 0;
-        seq[(int64_t)r * T + t] = w;
-        seqlp[(int64_t)r * T + t] = lp;
-        next_tok[r] = w;
-        if (unf && n_unfinished) *n_unfinished = 1;               // a flag, not a count (see decode_pick_kernel)
+        file_token(r, t, T, t == 0 || unfinished[r], it, lp, seq, seqlp, next_tok, unfinished, n_unfinished);
     }
 }
 
@@ -276,10 +237,7 @@ SUBGC_API int subgc_decode_sample(const float* logits, int64_t ld, int n, int V,
             LAUNCH(PER_, P, kFirst, INT_MAX, 0);                                                                                       \
         }                                                                                                                              \
     } while (0)
-    if (per <= 4) LAUNCHES(4);
-    else if (per <= 16) LAUNCHES(16);
-    else if (per <= 40) LAUNCHES(40);
-    else LAUNCHES(64);
+    SUBGC_DISPATCH_PER(per, LAUNCHES);
 #undef LAUNCHES
 #undef LAUNCH
     return subgc::check_launch("subgc_decode_sample");

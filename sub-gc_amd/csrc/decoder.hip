@@ -8,6 +8,7 @@
 // misc/utils.py:115-124 (criterion), :174-200,234-235 (clip-norm, Adam).
 #include "common.h"
 #include "bf16_util.h"
+#include "criterion_rule.h"
 
 #include <algorithm>
 
@@ -277,20 +278,8 @@ __global__ __launch_bounds__(256) void log_softmax_kernel(float* __restrict__ x,
         return;
     }
     float v[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int c = threadIdx.x + j * 256;
-        v[j] = c < V ? p[c] : -INFINITY;
-    }
-    float mx = -INFINITY;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) mx = fmaxf(mx, v[j]);
-    mx = block_max(mx, sm);
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < PER; ++j) sum += (threadIdx.x + j * 256 < V) ? expf(v[j] - mx) : 0.f;
-    sum = block_sum(sum, sm);
-    const float lse = mx + logf(sum);
+    row_load<PER>(p, V, v);
+    const float lse = row_lse<PER>(v, V, sm, RowPlain{});
     if (lse_out) {                                                        // the row stays as it is: consumers subtract lse themselves
         if (threadIdx.x == 0) lse_out[r] = lse;
         return;
@@ -300,10 +289,6 @@ __global__ __launch_bounds__(256) void log_softmax_kernel(float* __restrict__ x,
         const int c = threadIdx.x + j * 256;
         if (c < V) p[c] = v[j] - lse;
     }
-}
-__device__ __forceinline__ void store_one(void* base, int64_t i, float v, int b16) {
-    if (b16) static_cast<uint16_t*>(base)[i] = (uint16_t)subgc_f2bf(v);
-    else static_cast<float*>(base)[i] = v;
 }
 __global__ __launch_bounds__(256) void log_softmax_bwd_kernel(const float* __restrict__ logp, const float* dout, void* dlogits,
                                                               int64_t ld, int rows, int V, const int32_t* __restrict__ active, int b16) {
@@ -321,25 +306,7 @@ __global__ __launch_bounds__(256) void log_softmax_bwd_kernel(const float* __res
     sum = block_sum(sum, sm);
     for (int c = threadIdx.x; c < V; c += blockDim.x) store_one(dlogits, o + c, d[c] - expf(lp[c]) * sum, b16);
 }
-__global__ __launch_bounds__(1024) void nll_fwd_kernel(const float* __restrict__ logp, const int64_t* __restrict__ target,
-                                                       int64_t t_stride, const float* __restrict__ mask, int64_t m_stride,
-                                                       float* __restrict__ loss, float* __restrict__ scratch2, int S, int T, int V,
-                                                       const float* __restrict__ den_override, const float* __restrict__ lse) {
-    __shared__ float sm[16];
-    float num = 0.f, den = 0.f;
-    for (int q = threadIdx.x; q < S * T; q += blockDim.x) {
-        const int s = q / T, t = q % T;
-        const float m = mask[(int64_t)s * m_stride + t];
-        int64_t w = target[(int64_t)s * t_stride + t];
-        w = w < 0 ? 0 : (w >= V ? V - 1 : w);
-        num += -(logp[(int64_t)q * V + w] - (lse ? lse[q] : 0.f)) * m;
-        den += m;
-    }
-    num = block_sum(num, sm);
-    den = block_sum(den, sm);
-    if (den_override) den = den_override[0];           // the criterion's denominator over rows this call does not see (packed decoder)
-    if (threadIdx.x == 0) { scratch2[0] = num; scratch2[1] = den; loss[0] = num / den; }
-}
+// the criterion itself (forward, and backward fused through the log-softmax) is criterion_rule.h with NllRule
 __global__ __launch_bounds__(256) void nll_bwd_kernel(const int64_t* __restrict__ target, int64_t t_stride,
                                                       const float* __restrict__ mask, int64_t m_stride,
                                                       const float* __restrict__ scratch2, const float* __restrict__ dloss,
@@ -350,41 +317,6 @@ __global__ __launch_bounds__(256) void nll_bwd_kernel(const int64_t* __restrict_
     int64_t w = target[(int64_t)s * t_stride + t];
     w = w < 0 ? 0 : (w >= V ? V - 1 : w);
     dlogp[(int64_t)q * V + w] = -mask[(int64_t)s * m_stride + t] / scratch2[1] * dloss[0];
-}
-// fused backward of loss = -sum(mask * logp[target]) / sum(mask) through the log-softmax:
-// dlogits[r, c] = dloss * mask_r / den * (exp(logp[r, c]) - [c == target_r]); rows that are masked or inactive get zeros.
-__global__ __launch_bounds__(256) void nll_logsoftmax_bwd_kernel(const float* __restrict__ logp, const int64_t* __restrict__ target,
-                                                                 int64_t t_stride, const float* __restrict__ mask, int64_t m_stride,
-                                                                 const float* __restrict__ scratch2, const float* __restrict__ dloss,
-                                                                 void* __restrict__ dlogits, int64_t ldo, int T, int V,
-                                                                 const int32_t* __restrict__ active, int b16, const float* __restrict__ lse, int vec) {
-    // b16: d(logits) is a GEMM operand only (weight gradient and d(hidden)): written bf16, half the bytes of the largest tensor
-    // lse != NULL: `logp` holds RAW logits and lse[r] their row log-sum-exp (subgc_row_lse_f32): exp(x - lse) is the same number
-    // vec: V % 4 == 0 and 16-byte aligned rows on both sides -> four columns per lane (16-byte loads, 8/16-byte stores)
-    const int r = blockIdx.x, s = r / T, t = r % T;
-    const float m = mask[(int64_t)s * m_stride + t];
-    const int64_t d = (int64_t)r * ldo;
-    if (m == 0.f || (active && !active[r])) {
-        if (vec) { const float z[4] = {0.f, 0.f, 0.f, 0.f}; for (int c = threadIdx.x * 4; c < V; c += blockDim.x * 4) subgc_store_act<4>(dlogits, d + c, z, b16); }
-        else for (int c = threadIdx.x; c < V; c += blockDim.x) store_one(dlogits, d + c, 0.f, b16);
-        return;
-    }
-    int64_t w = target[(int64_t)s * t_stride + t];
-    w = w < 0 ? 0 : (w >= V ? V - 1 : w);
-    const float g = dloss[0] * m / scratch2[1];
-    const float* lp = logp + (int64_t)r * V;
-    const float sub = lse ? lse[r] : 0.f;
-    if (vec) {
-        for (int c = threadIdx.x * 4; c < V; c += blockDim.x * 4) {
-            const float4 x = *reinterpret_cast<const float4*>(lp + c);
-            const int wi = (int)w - c;
-            const float o[4] = {g * (expf(x.x - sub) - (wi == 0 ? 1.f : 0.f)), g * (expf(x.y - sub) - (wi == 1 ? 1.f : 0.f)),
-                                g * (expf(x.z - sub) - (wi == 2 ? 1.f : 0.f)), g * (expf(x.w - sub) - (wi == 3 ? 1.f : 0.f))};
-            subgc_store_act<4>(dlogits, d + c, o, b16);
-        }
-        return;
-    }
-    for (int c = threadIdx.x; c < V; c += blockDim.x) store_one(dlogits, d + c, g * (expf(lp[c] - sub) - (c == (int)w ? 1.f : 0.f)), b16);
 }
 __global__ __launch_bounds__(256) void step_active_kernel(const int64_t* __restrict__ labels, int64_t l_stride, int S, int T,
                                                           int32_t* __restrict__ active) {
@@ -409,21 +341,6 @@ __global__ __launch_bounds__(256) void step_active_kernel(const int64_t* __restr
 }
 
 // ------------------------------------------------------------------ token choice (decode)
-__device__ __forceinline__ void block_argmax(float& v, int& i, float* sv, int* si) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(i, o, 64);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { sv[w] = v; si[w] = i; }
-    __syncthreads();
-    v = sv[0]; i = si[0];
-    for (int k = 1; k < nw; ++k)
-        if (sv[k] > v || (sv[k] == v && si[k] < i)) { v = sv[k]; i = si[k]; }
-}
 constexpr int MAXK = 8;
 // One workgroup per row.  The row (<= 256*PER logits) is loaded into registers ONCE, with every load in flight together:
 // the first version walked the row two to k+3 times with dependent strided loads and cost 20 us for ten 38 KB rows --
@@ -441,39 +358,16 @@ __global__ __launch_bounds__(256) void decode_pick_kernel(const float* __restric
     const int r = blockIdx.x;
     const float* p = logp + (int64_t)r * ld;
     float x[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int c = threadIdx.x + j * 256;
-        x[j] = c < V ? p[c] : -INFINITY;
-    }
+    row_load<PER>(p, V, x);
     int it; float lp;
     if (k <= 0) {
-        float bv = -INFINITY; int bi = 0x7fffffff;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int c = threadIdx.x + j * 256;
-            if (c < V && (x[j] > bv || bi == 0x7fffffff)) { bv = x[j]; bi = c; }
-        }
-        block_argmax(bv, bi, sv, si);
-        it = bi; lp = bv;
-        if (raw) {                                // raw logits: log_softmax(x)[argmax] = -log sum exp(x - max)
-            float sum = 0.f;
-#pragma unroll
-            for (int j = 0; j < PER; ++j) sum += (threadIdx.x + j * 256 < V) ? expf(x[j] - bv) : 0.f;
-            sum = block_sum(sum, smf);
-            lp = -logf(sum);
-        }
+        row_greedy<PER>(x, V, raw, sv, si, smf, it, lp);
     } else {
-        // lp' = log_softmax(logp / temp)
-        float mx = -INFINITY;
+        // lp' = log_softmax(logp / temp): the row is divided in place ONCE (every later pass reads the tempered registers), so the
+        // reduction is the plain one -- decode_sample and sc_pick divide at each use instead (RowTempered)
 #pragma unroll
-        for (int j = 0; j < PER; ++j) { x[j] = x[j] / temp; mx = fmaxf(mx, x[j]); }
-        mx = block_max(mx, smf);
-        float sum = 0.f;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) sum += (threadIdx.x + j * 256 < V) ? expf(x[j] - mx) : 0.f;
-        sum = block_sum(sum, smf);
-        const float lse = mx + logf(sum);
+        for (int j = 0; j < PER; ++j) x[j] = x[j] / temp;
+        const float lse = row_lse<PER>(x, V, smf, RowPlain{});
         int top_i[MAXK]; float top_v[MAXK];
         if (k <= 3) {
             // k <= 3 (the_k = 3, opts.py): ONE pass keeps every thread's own three best in registers (the global top-3 is a subset of
@@ -531,17 +425,7 @@ __global__ __launch_bounds__(256) void decode_pick_kernel(const float* __restric
         pick = min(pick, k - 1);
         it = top_i[pick]; lp = top_v[pick];
     }
-    if (threadIdx.x == 0) {
-        int unf = (t == 0) ? (it > 0) : (unfinished[r] && it > 0);
-        unfinished[r] = unf;
-        const int64_t w = unf ? it : 0;
-        seq[(int64_t)r * T + t] = w;
-        seqlp[(int64_t)r * T + t] = lp;
-        next_tok[r] = w;
-        // a FLAG, not a count: every consumer only tests it against zero, and one same-address device atomic per row is what this
-        // kernel used to spend its time on (2560 rows x ~15 ns of memory-side serialisation = 38 of its 43 us)
-        if (unf && n_unfinished) *n_unfinished = 1;
-    }
+    if (threadIdx.x == 0) file_token(r, t, T, t == 0 || unfinished[r], it, lp, seq, seqlp, next_tok, unfinished, n_unfinished);
 }
 
 // ------------------------------------------------------------------ dropout masks (Philox-4x32-10)
@@ -920,10 +804,9 @@ SUBGC_API int subgc_log_softmax_rows(float* x, int64_t ldx, int rows, int V, con
     subgc::ProfScope prof(SUBGC_FAM_SOFTMAX, s, 4.0 * rows * (double)V * 2);
     SUBGC_REQUIRE(V <= 256 * 64, "log_softmax_rows: at most %d columns", 256 * 64);
     const int per = (V + 255) / 256;
-    if (per <= 4) hipLaunchKernelGGL(log_softmax_kernel<4>, dim3(rows), dim3(256), 0, s, x, ldx, rows, V, active, (float*)nullptr);
-    else if (per <= 16) hipLaunchKernelGGL(log_softmax_kernel<16>, dim3(rows), dim3(256), 0, s, x, ldx, rows, V, active, (float*)nullptr);
-    else if (per <= 40) hipLaunchKernelGGL(log_softmax_kernel<40>, dim3(rows), dim3(256), 0, s, x, ldx, rows, V, active, (float*)nullptr);
-    else hipLaunchKernelGGL(log_softmax_kernel<64>, dim3(rows), dim3(256), 0, s, x, ldx, rows, V, active, (float*)nullptr);
+#define LAUNCH(P) hipLaunchKernelGGL(log_softmax_kernel<P>, dim3(rows), dim3(256), 0, s, x, ldx, rows, V, active, (float*)nullptr)
+    SUBGC_DISPATCH_PER(per, LAUNCH);
+#undef LAUNCH
     return subgc::check_launch("subgc_log_softmax_rows");
 }
 SUBGC_API int subgc_row_lse_f32(const float* x, int64_t ldx, int rows, int V, float* lse, void* stream) {
@@ -935,10 +818,9 @@ SUBGC_API int subgc_row_lse_f32(const float* x, int64_t ldx, int rows, int V, fl
     subgc::ProfScope prof(SUBGC_FAM_SOFTMAX, s, 4.0 * rows * (double)V);
     float* xm = const_cast<float*>(x);                                    // the kernel does not write the row when lse_out is given
     const int per = (V + 255) / 256;
-    if (per <= 4) hipLaunchKernelGGL(log_softmax_kernel<4>, dim3(rows), dim3(256), 0, s, xm, ldx, rows, V, (const int32_t*)nullptr, lse);
-    else if (per <= 16) hipLaunchKernelGGL(log_softmax_kernel<16>, dim3(rows), dim3(256), 0, s, xm, ldx, rows, V, (const int32_t*)nullptr, lse);
-    else if (per <= 40) hipLaunchKernelGGL(log_softmax_kernel<40>, dim3(rows), dim3(256), 0, s, xm, ldx, rows, V, (const int32_t*)nullptr, lse);
-    else hipLaunchKernelGGL(log_softmax_kernel<64>, dim3(rows), dim3(256), 0, s, xm, ldx, rows, V, (const int32_t*)nullptr, lse);
+#define LAUNCH(P) hipLaunchKernelGGL(log_softmax_kernel<P>, dim3(rows), dim3(256), 0, s, xm, ldx, rows, V, (const int32_t*)nullptr, lse)
+    SUBGC_DISPATCH_PER(per, LAUNCH);
+#undef LAUNCH
     return subgc::check_launch("subgc_row_lse_f32");
 }
 SUBGC_API int subgc_log_softmax_rows_bwd(const float* logp, const float* dout, void* dlogits, int64_t ld, int rows, int V,
@@ -957,8 +839,8 @@ SUBGC_API int subgc_masked_nll_fwd(const float* logp, const int64_t* target, int
     SUBGC_REQUIRE(S > 0 && T > 0 && V > 0, "masked_nll_fwd: bad sizes");
     SUBGC_REQUIRE(logp && target && mask && loss && scratch2, "masked_nll_fwd: null pointer");
     SUBGC_DEBUG_RANGE(target, 8, S, T, t_stride, 0, V - 1, -1, "masked_nll_fwd: target (word ids)", stream);
-    hipLaunchKernelGGL(nll_fwd_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, logp, target, t_stride, mask, m_stride, loss,
-                       scratch2, S, T, V, den_override, lse);
+    hipLaunchKernelGGL((criterion_fwd_kernel<NllRule, 1024>), dim3(1), dim3(1024), 0, (hipStream_t)stream, logp, target, t_stride, mask,
+                       m_stride, NllRule{}, loss, scratch2, S, T, V, den_override, lse);
     return subgc::check_launch("subgc_masked_nll_fwd");
 }
 SUBGC_API int subgc_masked_nll_bwd(const int64_t* target, int64_t t_stride, const float* mask, int64_t m_stride, const float* scratch2,
@@ -979,13 +861,8 @@ SUBGC_API int subgc_nll_logsoftmax_bwd(const float* logp, const int64_t* target,
     SUBGC_REQUIRE(S > 0 && T > 0 && V > 0 && ld_out >= V, "nll_logsoftmax_bwd: bad sizes");
     SUBGC_REQUIRE(logp && target && mask && scratch2 && dloss && dlogits, "nll_logsoftmax_bwd: null pointer");
     SUBGC_DEBUG_RANGE(target, 8, S, T, t_stride, 0, V - 1, -1, "nll_logsoftmax_bwd: target (word ids)", stream);
-    hipStream_t s = (hipStream_t)stream;
-    subgc::ProfScope prof(SUBGC_FAM_SOFTMAX, s, 4.0 * S * T * (double)V * 2);
-    const int vec = V % 4 == 0 && ld_out % 4 == 0 && (reinterpret_cast<uintptr_t>(logp) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(dlogits) & (out_bf16 ? 7 : 15)) == 0;
-    hipLaunchKernelGGL(nll_logsoftmax_bwd_kernel, dim3(S * T), dim3(256), 0, s, logp, target, t_stride, mask, m_stride, scratch2, dloss,
-                       dlogits, ld_out, T, V, active, out_bf16, lse, vec);
-    return subgc::check_launch("subgc_nll_logsoftmax_bwd");
+    return criterion_logsoftmax_bwd_launch("subgc_nll_logsoftmax_bwd", logp, target, t_stride, mask, m_stride, NllRule{}, scratch2, dloss, dlogits,
+                                           ld_out, S, T, V, active, out_bf16, lse, stream);
 }
 SUBGC_API int subgc_step_active(const int64_t* labels, int64_t l_stride, int S, int T, int32_t* active, void* stream) {
     SUBGC_REQUIRE(S > 0 && T > 0 && T <= 512, "step_active: bad sizes");
@@ -1005,10 +882,7 @@ SUBGC_API int subgc_decode_pick(const float* logp, int64_t ld, int n, int V, int
     const int per = (V + 255) / 256;
 #define LAUNCH(P) hipLaunchKernelGGL(decode_pick_kernel<P>, dim3(n), dim3(256), 0, (hipStream_t)stream, logp, ld, n, V, k, temp, u, t, seq, \
                                      seqlp, T, next_tok, unfinished, n_unfinished, prev_count, raw_logits)
-    if (per <= 4) LAUNCH(4);
-    else if (per <= 16) LAUNCH(16);
-    else if (per <= 40) LAUNCH(40);
-    else LAUNCH(64);
+    SUBGC_DISPATCH_PER(per, LAUNCH);
 #undef LAUNCH
     return subgc::check_launch("subgc_decode_pick");
 }

@@ -1,28 +1,14 @@
 // Forced decode (include/subgc_forced_hip.h): the token filing of a decode step that FOLLOWS a given token (AttModel.py:295-316 with `it`
-// given) and the per-caption log-likelihood after the loop.  forced_pick_kernel is sc_pick_kernel's bookkeeping (selfcritical.hip) with
-// the choice replaced by the given token; its log-sum-exp takes that kernel's chunk-then-scan order (the row staged in LDS, a contiguous
-// chunk per lane, an inclusive scan over the 256 chunk sums).  No atomics: every output has one writer.
+// given) and the per-caption log-likelihood after the loop.  forced_pick_kernel files the given token with the pick kernels' file_token
+// (rowwise.h) behind its own test for a row that has ended; its log-sum-exp takes the chunk-then-scan order of sc_pick_kernel's sampling
+// half (the row staged in LDS, a contiguous chunk per lane, an inclusive scan over the 256 chunk sums), not the strided order of row_lse,
+// so its seqlp agrees with the greedy kernels' to rounding and not to the bit.  No atomics: every output has one writer.
 #include "common.h"
+#include "rowwise.h"
 
 #include "../../include/subgc_forced_hip.h"
 
 namespace {
-
-// inclusive scan over the 256 threads in thread order (a fixed tree per wave, the wave totals in front added in wave order); sm: >= 4 floats
-__device__ __forceinline__ float block_scan_incl(float v, float* sm) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    __syncthreads();
-    if (lane == 63) sm[w] = v;
-    __syncthreads();
-    float base = 0.f;
-    for (int i = 0; i < w; ++i) base += sm[i];
-    return base + v;
-}
 
 // One workgroup of 256 per row.  Every branch is workgroup-uniform (live, raw), so the block reductions run on full waves.
 // Dynamic LDS: V floats when raw (the row, read once).
@@ -65,14 +51,7 @@ __global__ __launch_bounds__(256) void forced_pick_kernel(const float* __restric
     } else {
         lp = p[tok];
     }
-    if (tid == 0) {
-        const int unf = tok > 0;
-        unfinished[r] = unf;
-        seq[o] = tok;
-        seqlp[o] = lp;
-        next_tok[r] = tok;
-        if (unf && n_unfinished) *n_unfinished = 1;               // a flag, not a count (see decode_pick_kernel)
-    }
+    if (tid == 0) file_token(r, t, T, live, tok, lp, seq, seqlp, next_tok, unfinished, n_unfinished);
 }
 
 // one thread per row: the live steps are a prefix (step 0, then as long as the previous token is a word)

@@ -1,10 +1,11 @@
 // Self-critical sequence training: RewardCriterion of misc/utils.py:89-109, the token choice of its rollout (AttModel.py:295-316 plus the
 // sample_max = 0 branch of the upstream project) and the reward of a rollout (opts.py:149-152).  Entry points and arithmetic:
-// include/subgc_selfcritical_hip.h.  The criterion kernels are the reward-weighted twins of nll_fwd_kernel and nll_logsoftmax_bwd_kernel
-// in decoder.hip, the greedy half of sc_pick_kernel is decode_pick_kernel's k = 0 branch and its sampling half follows multinomial_kernel
-// in sched_sampling.hip (the row staged in LDS, contiguous chunks per lane); those stay as they are.
+// include/subgc_selfcritical_hip.h.  The criterion on the decoder's rows is criterion_rule.h with RewardRule; the greedy half of
+// sc_pick_kernel and its token filing are the row helpers of rowwise.h that decode_pick_kernel uses, and its sampling half follows
+// multinomial_kernel in sched_sampling.hip (the row staged in LDS, contiguous chunks per lane).
 #include "common.h"
 #include "bf16_util.h"
+#include "criterion_rule.h"
 
 #include "../../include/subgc_metrics_hip.h"
 #include "../../include/subgc_selfcritical_hip.h"
@@ -12,45 +13,6 @@
 #include <cmath>
 
 namespace {
-
-__device__ __forceinline__ void store_one(void* base, int64_t i, float v, int b16) {
-    if (b16) static_cast<uint16_t*>(base)[i] = (uint16_t)subgc_f2bf(v);
-    else static_cast<float*>(base)[i] = v;
-}
-
-// first arg-max over the workgroup: (value descending, index ascending), the order of decode_pick_kernel
-__device__ __forceinline__ void block_argmax(float& v, int& i, float* sv, int* si) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(v, o, 64);
-        const int oi = __shfl_xor(i, o, 64);
-        if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-    }
-    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { sv[w] = v; si[w] = i; }
-    __syncthreads();
-    v = sv[0]; i = si[0];
-    for (int k = 1; k < nw; ++k)
-        if (sv[k] > v || (sv[k] == v && si[k] < i)) { v = sv[k]; i = si[k]; }
-}
-// exclusive scan over the 256 threads in thread order (a fixed tree per wave, the wave totals added in wave order); sm: >= 4 floats
-__device__ __forceinline__ float block_scan_excl(float v, float* sm) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    float exc = __shfl_up(v, 1, 64);
-    if (lane == 0) exc = 0.f;
-    __syncthreads();
-    if (lane == 63) sm[w] = v;
-    __syncthreads();
-    float base = 0.f;
-    for (int i = 0; i < w; ++i) base += sm[i];
-    return base + exc;
-}
 
 // One workgroup per row, the row (<= 256 * PER logits) loaded into registers once.  Rows below n_sample draw, the others take the arg-max:
 // blockIdx.x < n_sample is workgroup-uniform, like every other branch here.  Dynamic LDS: V floats when the launch has sampling rows.
@@ -70,34 +32,13 @@ __global__ __launch_bounds__(256) void sc_pick_kernel(const float* __restrict__ 
     const int tid = threadIdx.x, r = blockIdx.x;
     const float* p = logits + (int64_t)r * ld;
     float x[PER];
-#pragma unroll
-    for (int j = 0; j < PER; ++j) {
-        const int c = tid + j * 256;
-        x[j] = c < V ? p[c] : -INFINITY;
-    }
+    row_load<PER>(p, V, x);
     int it; float lp;
-    if (r >= n_sample) {                          // decode_pick_kernel, k <= 0: the same steps, the same bits
-        float bv = -INFINITY; int bi = 0x7fffffff;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) {
-            const int c = tid + j * 256;
-            if (c < V && (x[j] > bv || bi == 0x7fffffff)) { bv = x[j]; bi = c; }
-        }
-        block_argmax(bv, bi, sv, si);
-        it = bi; lp = bv;
-        if (raw) {                                // raw logits: log_softmax(x)[argmax] = -log sum exp(x - max)
-            float sum = 0.f;
-#pragma unroll
-            for (int j = 0; j < PER; ++j) sum += (tid + j * 256 < V) ? expf(x[j] - bv) : 0.f;
-            sum = block_sum(sum, smf);
-            lp = -logf(sum);
-        }
+    if (r >= n_sample) {
+        row_greedy<PER>(x, V, raw, sv, si, smf, it, lp);
     } else {
-        float mx = -INFINITY;
-#pragma unroll
-        for (int j = 0; j < PER; ++j) mx = fmaxf(mx, x[j] / temp);
-        mx = block_max(mx, smf);
-        float sum = 0.f;
+        const float mx = row_max<PER>(x, smf, RowTempered{temp});
+        float sum = 0.f;                          // row_sum_exp spelled out: each term is also staged in LDS for the CDF
 #pragma unroll
         for (int j = 0; j < PER; ++j) {
             const int c = tid + j * 256;
@@ -126,15 +67,7 @@ __global__ __launch_bounds__(256) void sc_pick_kernel(const float* __restrict__ 
         it = min(s_pick, V - 1);
         lp = p[it] / temp - lse;                  // one element read again (the registers cannot be indexed by a run-time column)
     }
-    if (tid == 0) {
-        int unf = (t == 0) ? (it > 0) : (unfinished[r] && it > 0);
-        unfinished[r] = unf;
-        const int64_t w = unf ? it : 0;
-        seq[(int64_t)r * T + t] = w;
-        seqlp[(int64_t)r * T + t] = lp;
-        next_tok[r] = w;
-        if (unf && n_unfinished) *n_unfinished = 1;               // a flag, not a count (see decode_pick_kernel)
-    }
+    if (tid == 0) file_token(r, t, T, t == 0 || unfinished[r], it, lp, seq, seqlp, next_tok, unfinished, n_unfinished);
 }
 
 // one thread per rollout row (2 S of them): the scored row; the sampled half also writes its replay labels and its criterion mask
@@ -240,63 +173,6 @@ __global__ __launch_bounds__(256) void reward_nll_bwd_kernel(const int64_t* __re
     if (gpn && dgpn) dgpn[s] = (float)((double)dl * acc / (double)den);
 }
 
-// RewardCriterion fused on the decoder's rows: nll_fwd_kernel with the reward as a per-row weight
-__global__ __launch_bounds__(256) void reward_logits_fwd_kernel(const float* __restrict__ logp, const int64_t* __restrict__ target,
-                                                                int64_t t_stride, const float* __restrict__ mask, int64_t m_stride,
-                                                                const float* __restrict__ reward, int64_t r_stride, float* __restrict__ loss,
-                                                                float* __restrict__ scratch2, int S, int T, int V,
-                                                                const float* __restrict__ den_override, const float* __restrict__ lse) {
-    __shared__ float sm[16];
-    float num = 0.f, den = 0.f;
-    for (int q = threadIdx.x; q < S * T; q += blockDim.x) {
-        const int s = q / T, t = q % T;
-        const float m = mask[(int64_t)s * m_stride + t];
-        int64_t w = target[(int64_t)s * t_stride + t];
-        w = w < 0 ? 0 : (w >= V ? V - 1 : w);
-        num += -(logp[(int64_t)q * V + w] - (lse ? lse[q] : 0.f)) * reward[(int64_t)s * r_stride + t] * m;
-        den += m;
-    }
-    num = block_sum(num, sm);
-    den = block_sum(den, sm);
-    if (den_override) den = den_override[0];           // the criterion's denominator over rows this call does not see (packed decoder)
-    if (threadIdx.x == 0) { scratch2[0] = num; scratch2[1] = den; loss[0] = num / den; }
-}
-
-// fused through the log-softmax: dlogits[r, c] = g (exp(logp[r, c] - lse[r]) - [c == w]), g = dloss (reward m) / den; masked or inactive
-// rows get zeros.  b16 / lse / vec as in nll_logsoftmax_bwd_kernel.
-__global__ __launch_bounds__(256) void reward_logsoftmax_bwd_kernel(const float* __restrict__ logp, const int64_t* __restrict__ target,
-                                                                    int64_t t_stride, const float* __restrict__ mask, int64_t m_stride,
-                                                                    const float* __restrict__ reward, int64_t r_stride,
-                                                                    const float* __restrict__ scratch2, const float* __restrict__ dloss,
-                                                                    void* __restrict__ dlogits, int64_t ldo, int T, int V,
-                                                                    const int32_t* __restrict__ active, int b16, const float* __restrict__ lse,
-                                                                    int vec) {
-    const int r = blockIdx.x, s = r / T, t = r % T;
-    const float m = mask[(int64_t)s * m_stride + t];
-    const int64_t d = (int64_t)r * ldo;
-    if (m == 0.f || (active && !active[r])) {
-        if (vec) { const float z[4] = {0.f, 0.f, 0.f, 0.f}; for (int c = threadIdx.x * 4; c < V; c += blockDim.x * 4) subgc_store_act<4>(dlogits, d + c, z, b16); }
-        else for (int c = threadIdx.x; c < V; c += blockDim.x) store_one(dlogits, d + c, 0.f, b16);
-        return;
-    }
-    int64_t w = target[(int64_t)s * t_stride + t];
-    w = w < 0 ? 0 : (w >= V ? V - 1 : w);
-    const float g = dloss[0] * (reward[(int64_t)s * r_stride + t] * m) / scratch2[1];
-    const float* lp = logp + (int64_t)r * V;
-    const float sub = lse ? lse[r] : 0.f;
-    if (vec) {
-        for (int c = threadIdx.x * 4; c < V; c += blockDim.x * 4) {
-            const float4 x = *reinterpret_cast<const float4*>(lp + c);
-            const int wi = (int)w - c;
-            const float o[4] = {g * (expf(x.x - sub) - (wi == 0 ? 1.f : 0.f)), g * (expf(x.y - sub) - (wi == 1 ? 1.f : 0.f)),
-                                g * (expf(x.z - sub) - (wi == 2 ? 1.f : 0.f)), g * (expf(x.w - sub) - (wi == 3 ? 1.f : 0.f))};
-            subgc_store_act<4>(dlogits, d + c, o, b16);
-        }
-        return;
-    }
-    for (int c = threadIdx.x; c < V; c += blockDim.x) store_one(dlogits, d + c, g * (expf(lp[c] - sub) - (c == (int)w ? 1.f : 0.f)), b16);
-}
-
 }  // namespace
 
 SUBGC_API int subgc_sc_pick(const float* logits, int64_t ld, int n, int n_sample, int V, float temp, const float* u, int t, int64_t* seq,
@@ -317,10 +193,7 @@ SUBGC_API int subgc_sc_pick(const float* logits, int64_t ld, int n, int n_sample
         hipLaunchKernelGGL(sc_pick_kernel<P>, dim3(n), dim3(256), lds, (hipStream_t)stream, logits, ld, n_sample, V, temp, u, t, seq, \
                            seqlp, T, next_tok, unfinished, n_unfinished, prev_count, raw_logits);                                     \
     } while (0)
-    if (per <= 4) LAUNCH(4);
-    else if (per <= 16) LAUNCH(16);
-    else if (per <= 40) LAUNCH(40);
-    else LAUNCH(64);
+    SUBGC_DISPATCH_PER(per, LAUNCH);
 #undef LAUNCH
     return subgc::check_launch("subgc_sc_pick");
 }
@@ -370,8 +243,8 @@ SUBGC_API int subgc_reward_logits_fwd(const float* logp, const int64_t* target, 
     SUBGC_REQUIRE(S > 0 && T > 0 && V > 0, "reward_logits_fwd: bad sizes");
     SUBGC_REQUIRE(logp && target && mask && reward && loss && scratch2, "reward_logits_fwd: null pointer");
     SUBGC_DEBUG_RANGE(target, 8, S, T, t_stride, 0, V - 1, -1, "reward_logits_fwd: target (word ids)", stream);
-    hipLaunchKernelGGL(reward_logits_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, logp, target, t_stride, mask, m_stride, reward,
-                       r_stride, loss, scratch2, S, T, V, den_override, lse);
+    hipLaunchKernelGGL((criterion_fwd_kernel<RewardRule, 256>), dim3(1), dim3(256), 0, (hipStream_t)stream, logp, target, t_stride, mask,
+                       m_stride, RewardRule{reward, r_stride}, loss, scratch2, S, T, V, den_override, lse);
     return subgc::check_launch("subgc_reward_logits_fwd");
 }
 
@@ -382,11 +255,6 @@ SUBGC_API int subgc_reward_logsoftmax_bwd(const float* logp, const int64_t* targ
     SUBGC_REQUIRE(S > 0 && T > 0 && V > 0 && ld_out >= V, "reward_logsoftmax_bwd: bad sizes");
     SUBGC_REQUIRE(logp && target && mask && reward && scratch2 && dloss && dlogits, "reward_logsoftmax_bwd: null pointer");
     SUBGC_DEBUG_RANGE(target, 8, S, T, t_stride, 0, V - 1, -1, "reward_logsoftmax_bwd: target (word ids)", stream);
-    hipStream_t s = (hipStream_t)stream;
-    subgc::ProfScope prof(SUBGC_FAM_SOFTMAX, s, 4.0 * S * T * (double)V * 2);
-    const int vec = V % 4 == 0 && ld_out % 4 == 0 && (reinterpret_cast<uintptr_t>(logp) & 15) == 0 &&
-                    (reinterpret_cast<uintptr_t>(dlogits) & (out_bf16 ? 7 : 15)) == 0;
-    hipLaunchKernelGGL(reward_logsoftmax_bwd_kernel, dim3(S * T), dim3(256), 0, s, logp, target, t_stride, mask, m_stride, reward, r_stride,
-                       scratch2, dloss, dlogits, ld_out, T, V, active, out_bf16, lse, vec);
-    return subgc::check_launch("subgc_reward_logsoftmax_bwd");
+    return criterion_logsoftmax_bwd_launch("subgc_reward_logsoftmax_bwd", logp, target, t_stride, mask, m_stride, RewardRule{reward, r_stride},
+                                           scratch2, dloss, dlogits, ld_out, S, T, V, active, out_bf16, lse, stream);
 }

@@ -1040,23 +1040,17 @@ class DecoderFn(Function):
                        step_c_att=C1[1:].clone(), step_c_lang=C2[1:].clone(), step_alpha=AL.clone(),
                        step_logp=logits3.permute(1, 0, 2).clone(), fed_tokens=tokens[:, :T].t().clone())
         crit = meta.get("crit")                      # (target [S,T] view, mask [S,T] view): criterion fused in
-        smoothing = meta.get("smoothing", 0.0)       # > 0: LabelSmoothing (misc/utils.py:126-156) in the place of LanguageModelCriterion
-        reward = meta.get("reward") if crit is not None else None      # [S,T] view: RewardCriterion (misc/utils.py:89-109) in that place
-        if reward is not None:
-            loss, nll_scratch = ops.reward_logits_fwd(logits.view(S, T, V1), crit[0], crit[1], reward)
-        elif crit is not None and smoothing > 0:
-            # rows after the early break are zero rows (`active`): lp = 0, so a masked-in one adds m * H, as in the reference
-            _, slp = ops.row_lse_sum(logits, raw=False)
-            loss, nll_scratch = ops.smoothed_nll_fwd(logits.view(S, T, V1), crit[0], crit[1], slp, smoothing)
-        elif crit is not None:
-            loss, nll_scratch = ops.masked_nll_fwd(logits.view(S, T, V1), crit[0], crit[1])
+        if crit is not None:
+            # smoothed: rows after the early break are zero rows (`active`): lp = 0, so a masked-in one adds m * H, as in the reference
+            rule = ops.Criterion(meta.get("smoothing", 0.0), meta.get("reward"))      # misc/utils.py:126-156 / 89-109 ([S,T] view)
+            _, slp = rule.row_pass(logits, raw=False)
+            loss, nll_scratch = rule.fwd(logits.view(S, T, V1), crit[0], crit[1], slp)
         else:
-            loss, nll_scratch = torch.zeros((), device=dev), None
+            rule, loss, nll_scratch = None, torch.zeros((), device=dev), None
         ctx.meta = (N, scale, S, T, R, E, A, V1)
         ctx.masks = (k_xt, k_out)
         ctx.pr = pr
-        ctx.crit, ctx.smoothing, ctx.reward = crit, smoothing, reward
-        ctx.nll_scratch = nll_scratch
+        ctx.crit, ctx.rule, ctx.nll_scratch = crit, rule, nll_scratch
         ctx.params, ctx.W, ctx.bf = P, W, bf
         ctx.set_materialize_grads(False)
         ctx.tokens_used = tokens
@@ -1112,14 +1106,7 @@ class DecoderFn(Function):
             for j in (i, also):
                 ops.copy2d(tmp, out_for(j).view(1, -1), accumulate=acc[j])
 
-        def crit_bwd(dst_):                               # d(logits) of the fused criterion: NLL, its smoothed or its reward-weighted twin
-            if ctx.reward is not None:
-                return ops.reward_logsoftmax_bwd(logp, ctx.crit[0], ctx.crit[1], ctx.reward, ctx.nll_scratch, dloss.contiguous(), dst_, active,
-                                                 S, T, V1)
-            if ctx.smoothing > 0:
-                return ops.smoothed_logsoftmax_bwd(logp, ctx.crit[0], ctx.crit[1], ctx.nll_scratch, dloss.contiguous(), ctx.smoothing, dst_, active,
-                                                   S, T, V1)
-            return ops.nll_logsoftmax_bwd(logp, ctx.crit[0], ctx.crit[1], ctx.nll_scratch, dloss.contiguous(), dst_, active, S, T, V1)
+        crit_bwd = lambda dst_: ctx.rule.bwd(logp, ctx.crit[0], ctx.crit[1], ctx.nll_scratch, dloss.contiguous(), dst_, active, S, T, V1)
 
         if ctx.crit is not None and dloss is not None and dout is None:
             # d(logits) only feeds the logit layer's two gradient GEMMs and its bias sum: written bf16 under compute_dtype = bf16

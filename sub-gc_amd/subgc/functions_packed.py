@@ -169,34 +169,25 @@ class PackedDecoderLossFn(Function):
         elif T_live > 0:
             op = ot[T_live - 1]
             ops.gemm(Hout[op:rows], W[21], logits[op:rows], tb=True, bias=lg_b)
-        smoothing = meta.get("smoothing", 0.0)                            # > 0: LabelSmoothing (misc/utils.py:126-156)
-        if smoothing > 0:
-            lse, slp = ops.row_lse_sum(logits[:rows])                     # the same row pass, one more scalar per row: sum_c (x - lse)
-        else:
-            lse = ops.row_lse(logits[:rows])                              # log_softmax without the write: the loss needs lse and one logit per row
+        rule = ops.Criterion(meta.get("smoothing", 0.0), meta.get("reward"))      # LabelSmoothing / RewardCriterion (misc/utils.py:126-156, 89-109)
+        lse, slp = rule.row_pass(logits[:rows], raw=True)      # no log_softmax write: the loss needs lse (smoothed: and slp) and one logit per row
         # criterion over the packed rows: row ot[t] + s  <->  (sentence perm[s], step t); the denominator is the sum of ALL mask
         # entries (dead ones included: the early break can cut live mask entries off), which the plan kernel computed
         tgt_p, msk_p = tgt_all[:max(rows, 1)], msk_all[:max(rows, 1)]
-        reward = meta.get("reward")                                       # [S, T] view: RewardCriterion (misc/utils.py:89-109)
-        rwd_p = None
-        if reward is not None:
+        if rule.reward is not None:
             # the reward of every packed row: subgc_packed_rows gathers its float operand as it is, so a second call with the reward in
             # the mask's place packs it in the same order; the plan itself has only seen the 0/1 mask
-            rwd_p = ops.packed_rows(labels, target, reward, plan.perm32, plan.offs, lens, idx if idx.stride(1) == 1 else idx.contiguous(),
-                                    img)[3][:max(rows, 1)]
-            loss, nll = ops.reward_logits_fwd(logits[:rows].view(rows, 1, V1), tgt_p, msk_p, rwd_p, den=plan.den, lse=lse)
-        elif smoothing > 0:
-            # the rows not given are the mask-0 tail and the reference's zero rows after its early break: a masked-in one of those adds
-            # m * H to the numerator, which the kernel takes from den - (mask sum of the rows given)
-            loss, nll = ops.smoothed_nll_fwd(logits[:rows].view(rows, 1, V1), tgt_p, msk_p, slp, smoothing, den=plan.den, lse=lse)
-        else:
-            loss, nll = ops.masked_nll_fwd(logits[:rows].view(rows, 1, V1), tgt_p, msk_p, den=plan.den, lse=lse)
+            rule.reward = ops.packed_rows(labels, target, rule.reward, plan.perm32, plan.offs, lens,
+                                          idx if idx.stride(1) == 1 else idx.contiguous(), img)[3][:max(rows, 1)]
+        # smoothed: the rows not given are the mask-0 tail and the reference's zero rows after its early break: a masked-in one of those
+        # adds m * H to the numerator, which the kernel takes from den - (mask sum of the rows given)
+        loss, nll = rule.fwd(logits[:rows].view(rows, 1, V1), tgt_p, msk_p, slp, den=plan.den, lse=lse)
 
         ctx.meta = (N, scale, S, T, T_live, R, E, A, V1, M, ot, rows)
-        ctx.masks, ctx.smoothing = (k_xt, k_out), smoothing
+        ctx.masks, ctx.rule = (k_xt, k_out), rule
         ctx.flat_tokens = (tok_flat, k_flat)
         ctx.W, ctx.bf = W, bf
-        ctx.pr, ctx.params, ctx.aux = pr, P, (plan, tokens_p, lens_p, tgt_p, msk_p, nll, lse, rwd_p)      # tokens_p: the words actually fed
+        ctx.pr, ctx.params, ctx.aux = pr, P, (plan, tokens_p, lens_p, tgt_p, msk_p, nll, lse)      # tokens_p: the words actually fed
         ctx.save_for_backward(fc_p, X_nodes, logits, xt, Gf, Wc1, Wc2, H1, H2, C1, C2, Hout, G1, G2, AH, AL)
         return loss
 
@@ -206,7 +197,7 @@ class PackedDecoderLossFn(Function):
         k_xt, k_out = ctx.masks
         tok_flat, k_flat = ctx.flat_tokens
         pr, P, W, bf = ctx.pr, ctx.params, ctx.W, ctx.bf
-        plan, labels_p, lens_p, tgt_p, msk_p, nll, lse, rwd_p = ctx.aux
+        plan, labels_p, lens_p, tgt_p, msk_p, nll, lse = ctx.aux
         (fc_p, X_nodes, logp, xt, Gf, Wc1, Wc2, H1, H2, C1, C2, Hout, G1, G2, AH, AL) = ctx.saved_tensors
         (fc0_w, fc0_b, fc2_w, fc2_b, att_w, att_b, c2a_w, c2a_b, emb, w1i, w1h, b1i, b1h, w2i, w2h, b2i, b2h,
          h2a_w, h2a_b, an_w, an_b, lg_w, lg_b) = P
@@ -247,12 +238,7 @@ class PackedDecoderLossFn(Function):
                 ops.copy2d(tmp, out_for(j).view(1, -1), accumulate=acc[j])
 
         dlogits = ops.empty_b16(max(rows, 1), V1, dev) if bf else new(max(rows, 1), V1)      # bf16: half the bytes of the largest tensor
-        if rwd_p is not None:
-            ops.reward_logsoftmax_bwd(logp[:rows], tgt_p, msk_p, rwd_p, nll, dloss.contiguous(), dlogits[:rows], None, rows, 1, V1, lse=lse)
-        elif ctx.smoothing > 0:
-            ops.smoothed_logsoftmax_bwd(logp[:rows], tgt_p, msk_p, nll, dloss.contiguous(), ctx.smoothing, dlogits[:rows], None, rows, 1, V1, lse=lse)
-        else:
-            ops.nll_logsoftmax_bwd(logp[:rows], tgt_p, msk_p, nll, dloss.contiguous(), dlogits[:rows], None, rows, 1, V1, lse=lse)
+        ctx.rule.bwd(logp[:rows], tgt_p, msk_p, nll, dloss.contiguous(), dlogits[:rows], None, rows, 1, V1, lse=lse)
         wgrad(21, dlogits[:rows], Hout[:rows], bias=22)
         F_.grads_ready("logit")                                 # logit.* is final: its all-reduce overlaps the whole BPTT loop
         dHout = new(max(rows, 1), R); ops.gemm(dlogits[:rows], W[21], dHout[:rows])

@@ -1528,6 +1528,33 @@ def reward_logsoftmax_bwd(logp, target, mask, reward, scratch, dloss, dlogits, a
     return dlogits
 
 
+class Criterion:
+    """The criterion fused on the decoder's rows, chosen once per decoder forward: RewardCriterion when `reward` ([S, T] view; the packed
+    decoder puts its packed rows there) is given, else LabelSmoothing when smoothing > 0, else LanguageModelCriterion."""
+
+    def __init__(self, smoothing=0.0, reward=None):
+        self.smoothing, self.reward = smoothing, reward
+
+    def row_pass(self, x, raw):                  # -> (lse, slp) for fwd, either may be None; raw: x holds logits, and every criterion needs lse
+        if self.smoothing > 0 and (raw or self.reward is None):
+            return row_lse_sum(x, raw=raw)
+        return (row_lse(x) if raw else None), None
+
+    def fwd(self, logp, target, mask, slp, den=None, lse=None):
+        if self.reward is not None:
+            return reward_logits_fwd(logp, target, mask, self.reward, den=den, lse=lse)
+        if self.smoothing > 0:
+            return smoothed_nll_fwd(logp, target, mask, slp, self.smoothing, den=den, lse=lse)
+        return masked_nll_fwd(logp, target, mask, den=den, lse=lse)
+
+    def bwd(self, logp, target, mask, scratch, dloss, dlogits, active, S, T, V, lse=None):
+        if self.reward is not None:
+            return reward_logsoftmax_bwd(logp, target, mask, self.reward, scratch, dloss, dlogits, active, S, T, V, lse=lse)
+        if self.smoothing > 0:
+            return smoothed_logsoftmax_bwd(logp, target, mask, scratch, dloss, self.smoothing, dlogits, active, S, T, V, lse=lse)
+        return nll_logsoftmax_bwd(logp, target, mask, scratch, dloss, dlogits, active, S, T, V, lse=lse)
+
+
 def step_active(labels, T):
     S = labels.size(0)
     active = torch.empty(S * T, device=labels.device, dtype=torch.int32)
