@@ -32,6 +32,8 @@ SELFCRITICAL_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "inc
 CONSENSUS_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_consensus_hip.h")
 # forced decode and grounding on ground-truth sentences (subgc_forced_*, subgc_gt_grounding_*): the eighth header, same arrangement
 FORCED_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_forced_hip.h")
+# the controllability experiment's input side (subgc_sct_*): the ninth header, same arrangement
+CONTROL_INPUT_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_control_input_hip.h")
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -105,7 +107,8 @@ def lib():
                             ("subgc_criterion_hip.h", parse_header(CRITERION_HEADER)),
                             ("subgc_selfcritical_hip.h", parse_header(SELFCRITICAL_HEADER)),
                             ("subgc_consensus_hip.h", parse_header(CONSENSUS_HEADER)),
-                            ("subgc_forced_hip.h", parse_header(FORCED_HEADER))):
+                            ("subgc_forced_hip.h", parse_header(FORCED_HEADER)),
+                            ("subgc_control_input_hip.h", parse_header(CONTROL_INPUT_HEADER))):
             for name, (ret, args) in protos.items():
                 try:
                     fn = getattr(L, name)
@@ -148,7 +151,7 @@ def _call_in(header, cache, name, args):
 
 
 _FN_METRICS, _FN_GROUNDING, _FN_CONTROLLABILITY, _FN_CRITERION, _FN_SELFCRITICAL, _FN_CONSENSUS = {}, {}, {}, {}, {}, {}
-_FN_FORCED = {}
+_FN_FORCED, _FN_CONTROL_INPUT = {}, {}
 
 
 def call_metrics(name, *args):
@@ -184,6 +187,11 @@ def call_consensus(name, *args):
 def call_forced(name, *args):
     """`call` for the entry points of subgc_forced_hip.h."""
     _call_in(FORCED_HEADER, _FN_FORCED, name, args)
+
+
+def call_control_input(name, *args):
+    """`call` for the entry points of subgc_control_input_hip.h."""
+    _call_in(CONTROL_INPUT_HEADER, _FN_CONTROL_INPUT, name, args)
 
 
 FAM = {"gemm": 1, "attn": 2, "lstm": 3, "gcn": 4, "pool": 5, "softmax": 6}

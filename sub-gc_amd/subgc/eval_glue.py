@@ -313,6 +313,29 @@ def _sample_batch(model, chunk, eval_kwargs, hold):
         return model.sample_images(chunk, opt=eval_kwargs)
 
 
+def control_images(model, raw, region_sets, set_off, img_wh, infos, ix_to_word, eval_kwargs=None, controllability=None, obj_num=None, rel_num=None,
+                   mode="greedy", gt=None, group=256):
+    """Controlled captioning from region boxes in one device pass: `control_input.assemble_sct_batch` (what the reference's
+    `dataloaders/dataloader_test_sct.py` `__getitem__` does per image on the host) and then the unchanged `caption_images` in `sct` mode on the
+    assembled items -- one caption per region set, in input order, scored with `controllability=` as `caption_images` describes.
+    raw / region_sets / set_off / img_wh / mode / gt: see `assemble_sct_batch`; obj_num / rel_num default to raw's own sizes (objects + 1
+    dummy node, 65 relation rows).  `eval_kwargs["sct"]` is set to 1.  Every entry additionally carries `"match"`: {'idx' [sets, R] int32,
+    'iou' [sets, R] fp32}, per region of each of the image's sets the matched detection box (-1: none) and its IoU."""
+    from .control_input import assemble_sct_batch
+    obj_num = int(raw["object_fmap"].size(1)) + 1 if obj_num is None else obj_num
+    rel_num = 65 if rel_num is None else rel_num
+    if len(infos) != raw["object_fmap"].size(0):
+        raise ValueError("control_images: one `infos` entry per image")
+    if not getattr(model, "sct", False):
+        raise ValueError("control_images: the model must be built with sct = 1 (every candidate sub-graph is decoded, no NMS)")
+    items, table = assemble_sct_batch(dict(raw, image_ids=[info["id"] for info in infos]), region_sets, set_off, img_wh, obj_num, rel_num, mode=mode, gt=gt)
+    preds = caption_images(model, items, infos, ix_to_word, dict(eval_kwargs or {}, sct=1), group=group, controllability=controllability)
+    seg = [int(v) for v in (set_off.tolist() if hasattr(set_off, "tolist") else set_off)]
+    for p, a, b in zip(preds, seg, seg[1:]):
+        p["match"] = {"idx": table["idx"][a:b], "iou": table["iou"][a:b]}
+    return preds
+
+
 def grounding_material(entry, boxes, wd_to_lemma, lemma_det_id_dict, det_id_to_det_wd, img_wh=None):
     """misc/grd_utils.py:36-58 for one `predictions` entry of `caption_images(..., return_att=1)`: the sentence ranked
     `entry["grounding"]["subg_index"]`, its words -> lemma -> detection class; for every word that names one, the box of the node
