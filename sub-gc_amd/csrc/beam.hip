@@ -7,6 +7,8 @@
 #include "common.h"
 #include "rowwise.h"
 
+#include "../../include/subgc_beam_att_hip.h"
+
 namespace {
 
 constexpr int TOPK_MAX = 32;
@@ -185,8 +187,13 @@ struct BeamStepArgs {
     int64_t* tok; int32_t* src;                          // [n][G][bd]: next input word, source row of every slot
     int t, T, G, bd, kk, unk, constraint, cap;
     float lam;
+    int32_t* anc; int32_t* done_anc;                     // ANC only: [n][G][T][bd] slot held after every word, [n][G][cap][T] of the finished
 };
 
+// ANC: the same step that also records every beam's ANCESTRY -- anc[r][vix] = the slot (0 .. bd-1 of its group) the beam now in slot
+// vix held after word r -- forked exactly as `seq` is, and filed with a finished beam (subgc_beam_step_anc).  Nothing the plain step
+// computes reads it, so the common outputs of the two instantiations are the same bits.
+template <bool ANC>
 __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepArgs a) {
     __shared__ float v[BS_MAXB * BS_MAXK], un[BS_MAXB * BS_MAXK];
     __shared__ int32_t id[BS_MAXB * BS_MAXK], ord[BS_MAXB * BS_MAXK];
@@ -196,6 +203,7 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepArgs a) {
     __shared__ float sel_p[BS_MAXB], sel_r[BS_MAXB];
     __shared__ int32_t tmp_seq[BS_MAXT * BS_MAXB];
     __shared__ float tmp_lps[BS_MAXT * BS_MAXB];
+    __shared__ int32_t tmp_anc[ANC ? BS_MAXT * BS_MAXB : 1];
     const int s = blockIdx.x, lane = threadIdx.x;
     const int G = a.G, bd = a.bd, kk = a.kk, T = a.T;
     for (int g = 0; g < G; ++g) {
@@ -209,6 +217,7 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepArgs a) {
         int32_t* seq = a.seq + sg * T * bd;
         float* lps = a.lps + sg * T * bd;
         float* sums = a.sums + sg * bd;
+        int32_t* anc = ANC ? a.anc + sg * T * bd : nullptr;
         for (int e = lane; e < bd * kk; e += 64) {                            // augment (:134-137, add_diversity :33-40)
             const int q = e / kk;
             float val = a.tv[sg * bd * kk + e];
@@ -224,6 +233,8 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepArgs a) {
             v[e] = val; un[e] = u0; id[e] = w;
         }
         for (int e = lane; e < tau * bd; e += 64) { tmp_seq[e] = seq[e]; tmp_lps[e] = lps[e]; }
+        if (ANC)
+            for (int e = lane; e < tau * bd; e += 64) tmp_anc[e] = anc[e];
         __syncthreads();
         if (lane < bd) {                                                      // stable descending order of the row (np.argsort(-vals, stable))
             const int q = lane;
@@ -260,8 +271,10 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepArgs a) {
             const int r = e / bd, vix = e % bd;
             seq[e] = tmp_seq[r * bd + sel_q[vix]];
             lps[e] = tmp_lps[r * bd + sel_q[vix]];
+            if (ANC) anc[e] = tmp_anc[r * bd + sel_q[vix]];
         }
         if (lane < bd) {
+            if (ANC) anc[tau * bd + lane] = lane;
             seq[tau * bd + lane] = sel_tok[lane];
             lps[tau * bd + lane] = sel_r[lane];
             sums[lane] = sel_p[lane];
@@ -277,6 +290,7 @@ __global__ __launch_bounds__(64) void beam_step_kernel(BeamStepArgs a) {
                         for (int r = 0; r < T; ++r) {
                             a.done_seq[(sg * a.cap + slot) * T + r] = r <= tau ? seq[r * bd + vix] : 0;
                             a.done_lps[(sg * a.cap + slot) * T + r] = r <= tau ? lps[r * bd + vix] : 0.f;
+                            if (ANC) a.done_anc[(sg * a.cap + slot) * T + r] = r <= tau ? anc[r * bd + vix] : 0;
                         }
                         a.done_p[sg * a.cap + slot] = sums[vix];
                         a.done_len[sg * a.cap + slot] = tau + 1;
@@ -297,7 +311,70 @@ SUBGC_API int subgc_beam_step(const float* tv, const int32_t* ti, int32_t* seq, 
                   "beam_step: need T <= 64, beams per group <= 16, kk <= 18");
     if (n == 0) return SUBGC_OK;
     SUBGC_REQUIRE(tv && ti && seq && lps && sums && done_cnt && done_seq && done_lps && done_p && done_len && tok && src, "beam_step: null pointer");
-    BeamStepArgs a{tv, ti, seq, lps, sums, done_cnt, done_seq, done_lps, done_p, done_len, tok, src, t, T, G, bd, kk, unk, constraint, cap, lam};
-    hipLaunchKernelGGL(beam_step_kernel, dim3(n), dim3(64), 0, (hipStream_t)stream, a);
+    BeamStepArgs a{tv, ti, seq, lps, sums, done_cnt, done_seq, done_lps, done_p, done_len, tok, src, t, T, G, bd, kk, unk, constraint, cap, lam,
+                   nullptr, nullptr};
+    hipLaunchKernelGGL(beam_step_kernel<false>, dim3(n), dim3(64), 0, (hipStream_t)stream, a);
     return subgc::check_launch("subgc_beam_step");
+}
+
+// ------------------------------------------------------------------ attention of the winning beams (subgc_beam_att_hip.h)
+SUBGC_API int subgc_beam_step_anc(const float* tv, const int32_t* ti, int32_t* seq, float* lps, float* sums, int32_t* done_cnt,
+                                  int32_t* done_seq, float* done_lps, float* done_p, int32_t* done_len, int32_t* anc, int32_t* done_anc,
+                                  int64_t* tok, int32_t* src, int n, int t, int T, int G, int bd, int kk, int unk, int constraint, float lam,
+                                  int cap, void* stream) {
+    SUBGC_REQUIRE(n >= 0 && T > 0 && T <= BS_MAXT && G > 0 && bd > 0 && bd <= BS_MAXB && kk >= 1 && kk <= BS_MAXK && cap > 0 && t >= 0,
+                  "beam_step_anc: need T <= 64, beams per group <= 16, kk <= 18");
+    if (n == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(tv && ti && seq && lps && sums && done_cnt && done_seq && done_lps && done_p && done_len && anc && done_anc && tok && src,
+                  "beam_step_anc: null pointer");
+    BeamStepArgs a{tv, ti, seq, lps, sums, done_cnt, done_seq, done_lps, done_p, done_len, tok, src, t, T, G, bd, kk, unk, constraint, cap, lam,
+                   anc, done_anc};
+    hipLaunchKernelGGL(beam_step_kernel<true>, dim3(n), dim3(64), 0, (hipStream_t)stream, a);
+    return subgc::check_launch("subgc_beam_step_anc");
+}
+
+namespace {
+constexpr int BA_MAXN = 4096;
+
+// One workgroup per (sub-graph, word position): whole attention rows copied, zero rows behind the beam's length.  The picks were
+// range-checked by the host and `len` / `anc` come from subgc_beam_step_anc; every index is clamped all the same.
+__global__ __launch_bounds__(64) void beam_att_gather_kernel(const float* __restrict__ al_step, int64_t ld_step, int steps, int rows, int N,
+                                                             const int32_t* __restrict__ done_anc, const int32_t* __restrict__ done_len,
+                                                             const int32_t* __restrict__ pick, int G, int bd, int cap, int T,
+                                                             float* __restrict__ out, int64_t ld_t, int64_t ld_row) {
+    const int s = blockIdx.x, w = blockIdx.y;
+    float* dst = out + (int64_t)w * ld_t + (int64_t)s * ld_row;
+    int g = pick[2 * s], j = pick[2 * s + 1];
+    g = g < 0 ? 0 : (g >= G ? G - 1 : g);
+    j = j < 0 ? 0 : (j >= cap ? cap - 1 : j);
+    const int64_t beam = ((int64_t)s * G + g) * cap + j;
+    int len = done_len[beam];
+    len = len > T ? T : len;
+    if (w >= len) {
+        for (int i = threadIdx.x; i < N; i += 64) dst[i] = 0.f;
+        return;
+    }
+    int step = 0, slot = 0;                                                   // word 0: the <bos> step, whose rows agree within a sub-graph
+    if (w > 0) { step = w + g; slot = done_anc[beam * T + w - 1]; }
+    step = step >= steps ? steps - 1 : step;
+    slot = slot < 0 ? 0 : (slot >= bd ? bd - 1 : slot);
+    int64_t row = ((int64_t)s * G + g) * bd + slot;
+    row = row >= rows ? rows - 1 : row;
+    const float* src = al_step + (int64_t)step * ld_step + row * N;
+    for (int i = threadIdx.x; i < N; i += 64) dst[i] = src[i];
+}
+}  // namespace
+
+SUBGC_API int subgc_beam_att_gather(const float* al_step, int64_t ld_step, int steps, int rows, int N, const int32_t* done_anc,
+                                    const int32_t* done_len, const int32_t* pick, int n, int G, int bd, int cap, int T, float* out,
+                                    int64_t ld_t, int64_t ld_row, void* stream) {
+    SUBGC_REQUIRE(n >= 0 && T > 0 && T <= BS_MAXT && G > 0 && bd > 0 && bd <= BS_MAXB && cap > 0, "beam_att_gather: need T <= 64, beams per group <= 16");
+    SUBGC_REQUIRE(N >= 1 && N <= BA_MAXN, "beam_att_gather: 1 <= N <= %d attention columns", BA_MAXN);
+    SUBGC_REQUIRE(steps >= T + G - 1 && rows == (int64_t)n * G * bd && ld_step >= (int64_t)rows * N && ld_row >= N && ld_t >= (int64_t)n * ld_row,
+                  "beam_att_gather: need T + G - 1 step slices of n * G * bd rows and non-overlapping output rows");
+    if (n == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(al_step && done_anc && done_len && pick && out, "beam_att_gather: null pointer");
+    hipLaunchKernelGGL(beam_att_gather_kernel, dim3(n, T + 1), dim3(64), 0, (hipStream_t)stream, al_step, ld_step, steps, rows, N, done_anc, done_len,
+                       pick, G, bd, cap, T, out, ld_t, ld_row);
+    return subgc::check_launch("subgc_beam_att_gather");
 }

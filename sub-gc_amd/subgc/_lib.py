@@ -34,6 +34,8 @@ CONSENSUS_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "includ
 FORCED_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_forced_hip.h")
 # the controllability experiment's input side (subgc_sct_*): the ninth header, same arrangement
 CONTROL_INPUT_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_control_input_hip.h")
+# attention of the winning beams (subgc_beam_step_anc, subgc_beam_att_gather): the tenth header, same arrangement
+BEAM_ATT_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_beam_att_hip.h")
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -108,7 +110,8 @@ def lib():
                             ("subgc_selfcritical_hip.h", parse_header(SELFCRITICAL_HEADER)),
                             ("subgc_consensus_hip.h", parse_header(CONSENSUS_HEADER)),
                             ("subgc_forced_hip.h", parse_header(FORCED_HEADER)),
-                            ("subgc_control_input_hip.h", parse_header(CONTROL_INPUT_HEADER))):
+                            ("subgc_control_input_hip.h", parse_header(CONTROL_INPUT_HEADER)),
+                            ("subgc_beam_att_hip.h", parse_header(BEAM_ATT_HEADER))):
             for name, (ret, args) in protos.items():
                 try:
                     fn = getattr(L, name)
@@ -151,7 +154,7 @@ def _call_in(header, cache, name, args):
 
 
 _FN_METRICS, _FN_GROUNDING, _FN_CONTROLLABILITY, _FN_CRITERION, _FN_SELFCRITICAL, _FN_CONSENSUS = {}, {}, {}, {}, {}, {}
-_FN_FORCED, _FN_CONTROL_INPUT = {}, {}
+_FN_FORCED, _FN_CONTROL_INPUT, _FN_BEAM_ATT = {}, {}, {}
 
 
 def call_metrics(name, *args):
@@ -192,6 +195,11 @@ def call_forced(name, *args):
 def call_control_input(name, *args):
     """`call` for the entry points of subgc_control_input_hip.h."""
     _call_in(CONTROL_INPUT_HEADER, _FN_CONTROL_INPUT, name, args)
+
+
+def call_beam_att(name, *args):
+    """`call` for the entry points of subgc_beam_att_hip.h."""
+    _call_in(BEAM_ATT_HEADER, _FN_BEAM_ATT, name, args)
 
 
 FAM = {"gemm": 1, "attn": 2, "lstm": 3, "gcn": 4, "pool": 5, "softmax": 6}

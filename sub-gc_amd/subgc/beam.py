@@ -42,10 +42,11 @@ def penalty_builder(cfg):
 
 class _Group:
     """One beam group of one sub-graph: the tables of CaptionModel.py:106-108."""
-    __slots__ = ("seq", "lps", "sums", "done")
+    __slots__ = ("seq", "lps", "sums", "done", "anc")
 
     def __init__(self, T, bd):
         self.seq = np.zeros((T, bd), np.int64)
+        self.anc = np.zeros((T, bd), np.int32)                                   # the slot every beam held after each of its words
         self.lps = np.zeros((T, bd), _F32)
         self.sums = np.zeros(bd, _F32)
         self.done = []
@@ -71,12 +72,14 @@ def _beam_step(grp, vals, idx, tau, bd, unk, constraint, earlier, lam):
             j = order[q, c]
             cands.append((_F32(grp.sums[q] + vals[q, j]), q, int(idx[q, j]), unaug[q, j]))
     cands.sort(key=lambda x: -x[0])                                              # stable, like sorted() at :73
-    prev_seq, prev_lps = grp.seq[:tau].copy(), grp.lps[:tau].copy()
+    prev_seq, prev_lps, prev_anc = grp.seq[:tau].copy(), grp.lps[:tau].copy(), grp.anc[:tau].copy()
     src = []
     for vix in range(bd):
         p, q, tok, r = cands[vix]
         grp.seq[:tau, vix] = prev_seq[:, q]
         grp.lps[:tau, vix] = prev_lps[:, q]
+        grp.anc[:tau, vix] = prev_anc[:, q]
+        grp.anc[tau, vix] = vix
         grp.seq[tau, vix] = tok
         grp.lps[tau, vix] = r
         grp.sums[vix] = p
@@ -87,15 +90,16 @@ def _beam_step(grp, vals, idx, tau, bd, unk, constraint, earlier, lam):
 class _BatchEngine:
     """All sub-graphs x beams of an image batch as rows of one DecodeState (the product path)."""
 
-    def __init__(self, pr, P, N, beam, xt_table=None, snapshots=None):
+    def __init__(self, pr, P, N, beam, xt_table=None, snapshots=None, return_att=False):
         n, dev = pr.S, pr.f.device
         self.n, self.rows, self.dev = n, n * beam, dev
         rep = torch.arange(n, device=dev).repeat_interleave(beam)
         prb = SimpleNamespace(S=self.rows, N=N, f=pr.f.index_select(0, rep).contiguous(), u=pr.u, v=pr.v,
                               off=pr.off.index_select(0, rep).contiguous(), lens=pr.lens.index_select(0, rep).contiguous())
         self.pr, self.prb, self.rep = pr, prb, rep
-        self.st = F_.DecodeState(prb, P, N, False, xt_table=xt_table, fuse_lstm=True, snapshots=snapshots)    # fused for <= 32 rows
+        self.st = F_.DecodeState(prb, P, N, bool(return_att), xt_table=xt_table, fuse_lstm=True, snapshots=snapshots)    # fused for <= 32 rows
         self.V1 = self.st.V1
+        self.alpha = torch.empty(self.rows, N, device=dev, dtype=torch.float32) if return_att else None    # host `search`: the last step's rows
 
     def refresh(self):
         """Re-derive the per-beam rows from `pr` and restart the recurrent state (hipGraph replay: `pr` was overwritten in place)."""
@@ -110,10 +114,16 @@ class _BatchEngine:
         return self.vals.cpu().numpy(), self.idx.cpu().numpy()
 
     def first(self, kk):                                                         # <bos>, AttModel.py:223-227
-        return self._topk(self.st.step(torch.zeros(self.rows, device=self.dev, dtype=torch.long), None, normalize=False), kk)
+        return self._topk(self.st.step(torch.zeros(self.rows, device=self.dev, dtype=torch.long), self.alpha, normalize=False), kk)
 
     def advance(self, tok, kk):
-        return self._topk(self.st.step(torch.from_numpy(tok).to(self.dev), None, normalize=False), kk)
+        return self._topk(self.st.step(torch.from_numpy(tok).to(self.dev), self.alpha, normalize=False), kk)
+
+    def attention(self):
+        """[rows, N] attention rows of the step `first` / `advance` just ran (host `search` with return_att)."""
+        if self.alpha is None:
+            raise ValueError("this engine was built without attention output (return_att)")
+        return self.alpha.cpu().numpy()
 
     def reorder(self, src):
         self.st.reorder(torch.from_numpy(src).to(self.dev))
@@ -148,6 +158,9 @@ class _StepEngine:
         logp, self.state = self.m.get_logprobs_state(torch.from_numpy(tok).to(self.dev), *self.args, self.state)
         return self._topk(logp, kk)
 
+    def attention(self):
+        raise ValueError("the step-API engine has no attention output: its <bos> step is the caller's (CaptionModel.beam_search)")
+
     def reorder(self, src):
         sel = torch.from_numpy(src.astype(np.int64)).to(self.dev)
         self.state = tuple(s.index_select(1, sel) for s in self.state)
@@ -163,21 +176,54 @@ class _StepEngine:
 
 
 @torch.no_grad()
-def beam_decode(pr, P, N, T, opt, xt_table=None, on_device=True):
+def beam_decode(pr, P, N, T, opt, xt_table=None, on_device=True, return_att=False):
     """Decode every sub-graph of `pr` (an F_.Prepared) with beam search.
     Returns (seq [n, T] int64, seqLogprobs [n, T] fp32, done_beams) -- CPU tensors, as the reference's are.
     `on_device` (default): the candidate bookkeeping runs in `subgc_beam_step`, the loop has no host round trip;
-    False keeps it on the host (`search`, the restatement the device kernel is tested against)."""
-    eng = _BatchEngine(pr, P, N, int(opt.get("beam_size", 10)), xt_table)
-    return search_device(eng, T, opt) if on_device else search(eng, T, opt)
+    False keeps it on the host (`search`, the restatement the device kernel is tested against).
+    `return_att`: a fourth element {"AL": fp32 [T + 1, n, N] (device tensor; numpy from the host `search`), "len": int array [n]}: the
+    attention rows of every sub-graph's winning beam, AL[w, s] = the distribution of the decoder step whose logits produced word w of
+    seq[s], zero for w >= len[s] (len counts the end token and is T for a beam cut at the last step).  Beam search never feeds its last
+    word (CaptionModel.py:170-171), so unlike a greedy decode there is no attention row behind the last word: AL[T] is all zero."""
+    eng = _BatchEngine(pr, P, N, int(opt.get("beam_size", 10)), xt_table, return_att=return_att)
+    return search_device(eng, T, opt, return_att) if on_device else search(eng, T, opt, return_att)
+
+
+def check_picks(pick, cnt):
+    """The host's range check in front of `subgc_beam_att_gather`: pick int [n, 2] = (group, finished-beam slot) per sub-graph, cnt int
+    [n, G] = the finished beams of every group.  Raises SubgcError naming the first offender; needs no GPU."""
+    from ._lib import SubgcError
+    pick, cnt = np.asarray(pick), np.asarray(cnt)
+    if pick.ndim != 2 or pick.shape[1] != 2 or cnt.ndim != 2 or pick.shape[0] != cnt.shape[0]:
+        raise SubgcError(f"beam attention: picks [n, 2] and finished-beam counts [n, G], got {pick.shape} and {cnt.shape}")
+    n, G = cnt.shape
+    for s in range(n):
+        g, j = int(pick[s, 0]), int(pick[s, 1])
+        if not 0 <= g < G:
+            raise SubgcError(f"beam attention: sub-graph {s} picks group {g}; the search has {G}")
+        if not 0 <= j < int(cnt[s, g]):
+            raise SubgcError(f"beam attention: sub-graph {s} picks finished beam {j} of group {g}, which finished {int(cnt[s, g])}")
+    return pick.astype(np.int32)
+
+
+def check_att_limits(T, bd, kk, N):
+    """The limits of subgc_beam_att_hip.h, refused on the host with the number in the text."""
+    from ._lib import SubgcError
+    if T > 64 or bd > 16 or kk > 18:
+        raise SubgcError(f"beam attention: T = {T}, beams per group = {bd}, leading columns = {kk}; the limits are T <= 64, bd <= 16, kk <= 18")
+    if not 1 <= N <= ops.BEAM_ATT_MAX_N:
+        raise SubgcError(f"beam attention: {N} attention columns; the limit is {ops.BEAM_ATT_MAX_N}")
 
 
 class DeviceTables:
     """The tables of CaptionModel.py:106-109 for n sub-graphs x G groups, resident on the device."""
 
-    def __init__(self, n, G, T, bd, dev):
+    def __init__(self, n, G, T, bd, dev, return_att=False):
         z = lambda *s, dt: ops.zero_(torch.empty(*s, device=dev, dtype=dt))
         self.cap = bd * T                                                         # a group finishes at most bd beams per step
+        # the ancestry tables of subgc_beam_step_anc (return_att): forked like `seq`, filed like `done_seq`; they stay on the device
+        self.anc = z(n, G, T, bd, dt=torch.int32) if return_att else None
+        self.done_anc = z(n, G, self.cap, T, dt=torch.int32) if return_att else None
         self.seq, self.lps, self.sums = z(n, G, T, bd, dt=torch.int32), z(n, G, T, bd, dt=torch.float32), z(n, G, bd, dt=torch.float32)
         # the finished-beam tables are views of ONE 4-byte buffer: `collect` brings them to the host with a single copy (five
         # synchronising copies cost 0.15 ms of a 2.8 ms one-image search)
@@ -223,13 +269,22 @@ class DeviceSearch:
     decoder step on the stream (`loop`: launches only, no host read, so it can be captured in a hipGraph); the host reads
     the finished beams once, after the last step (`collect`)."""
 
-    def __init__(self, eng, T, opt):
+    def __init__(self, eng, T, opt, return_att=False):
         self.eng, self.T, self.opt = eng, T, dict(opt)
         self.beam, self.G, self.bd, self.kk = _check(opt, eng)
         self.lam = float(_F32(opt.get("diversity_lambda", 0.5)))
         self.constraint = opt.get("decoding_constraint", 0)
         n, rows, dev, G, bd, kk = eng.n, eng.rows, eng.dev, self.G, self.bd, self.kk
-        self.tb = DeviceTables(n, G, T, bd, dev)
+        self.return_att = bool(return_att)
+        self.tb = DeviceTables(n, G, T, bd, dev, self.return_att)
+        self.AL_step = None
+        if self.return_att:
+            # step-major attention rows: slice 0 = the <bos> step, slice t + 1 = the decoder step of loop iteration t (the last
+            # iteration, T + G - 2, feeds nothing: T + G - 1 slices).  Histories are NOT reordered per step -- the ancestry table says
+            # on which row every word of a beam was produced, and one gather after the ranking reads exactly the winners' rows.
+            self.N = int(eng.st.N)
+            check_att_limits(T, bd, kk, self.N)
+            self.AL_step = ops.zero_(torch.empty(T + G - 1, rows, self.N, device=dev, dtype=torch.float32))
         self.tok = ops.zero_(torch.empty(rows, device=dev, dtype=torch.long))
         self.src = ops.zero_(torch.empty(rows, device=dev, dtype=torch.int32))
         self.tv = torch.empty(rows, kk, device=dev, dtype=torch.float32)
@@ -246,12 +301,14 @@ class DeviceSearch:
         if not fresh_tables:
             for x in (tb.seq, tb.lps, tb.sums, tb.done_cnt, tok):
                 ops.zero_(x)
-        ops.row_topk(eng.st.step(tok, None, normalize=False), kk, tv, ti, log_softmax=True)      # <bos>, AttModel.py:223-227
+        att = self.AL_step
+        step = ops.beam_step_anc if att is not None else ops.beam_step
+        ops.row_topk(eng.st.step(tok, None if att is None else att[0], normalize=False), kk, tv, ti, log_softmax=True)      # <bos>, AttModel.py:223-227
         if G > 1:
             init = eng.snapshot()
             tv4, ti4, nv4, ni4 = (x.view(n, G, bd, kk) for x in (tv, ti, self.nv, self.ni))
         for t in range(T + G - 1):
-            ops.beam_step(tv, ti, tb, tok, src, t, T, G, bd, kk, unk, self.constraint, self.lam)
+            step(tv, ti, tb, tok, src, t, T, G, bd, kk, unk, self.constraint, self.lam)
             if not any(g <= t + 1 <= T + g - 1 for g in range(G)):
                 break
             if G > 1 and 0 < t < G:                                               # group t starts now: give it the post-<bos> state
@@ -259,7 +316,7 @@ class DeviceSearch:
                 for cur, saved in zip(eng.st.recurrent(), init):
                     cur.index_copy_(0, sel, saved.index_select(0, sel))
             eng.st.reorder(src)
-            logits = eng.st.step(tok, None, normalize=False)
+            logits = eng.st.step(tok, None if att is None else att[t + 1], normalize=False)
             if G == 1:
                 ops.row_topk(logits, kk, tv, ti, log_softmax=True)
             else:
@@ -268,7 +325,10 @@ class DeviceSearch:
                     if g <= t <= T + g - 1:                                       # only the groups that stepped take the new rows
                         tv4[:, g], ti4[:, g] = nv4[:, g], ni4[:, g]
 
-    def collect(self):
+    def collect(self, which=(0, 0)):
+        """-> (seq, seqlp, done_beams) and, with return_att, a fourth element {"AL": fp32 [T + 1, n, N] on the device, "len": int32 [n]}
+        (see `beam_decode`) gathered by ONE launch behind the host's ranking.  `which` = (group g, rank r): the attention of the
+        kept beam done_beams[s][g * bd + r] of every sub-graph instead of the winner's (0, 0)."""
         tb, T, G, bd, n, opt = self.tb, self.T, self.G, self.bd, self.eng.n, self.opt
         length_penalty = penalty_builder(opt.get("length_penalty", ""))
         # one read of the finished beams; ranking (:174-175) vectorised, python objects only for the beams that are kept
@@ -293,19 +353,34 @@ class DeviceSearch:
         done_beams = [[{"seq": rs[k], "logps": rl[k], "unaug_p": top_un[k], "p": top_p[k]} for k in range(s * per, (s + 1) * per)]
                       for s in range(n)]
         seq, seqlp = top_seq[:, 0, 0].clone(), top_lps[:, 0, 0].clone()
-        return seq, seqlp, done_beams
+        if not self.return_att:
+            return seq, seqlp, done_beams
+        g, r = int(which[0]), int(which[1])
+        if not (0 <= g < G and 0 <= r < bd):
+            from ._lib import SubgcError
+            raise SubgcError(f"beam attention: kept beam (group {g}, rank {r}) of {G} group(s) x {bd} beam(s)")
+        pick = check_picks(np.stack([np.full(n, g, np.int64), order[:, g, r]], 1) if n else np.zeros((0, 2), np.int64), cnt)
+        lens = np.minimum(dlen[np.arange(n), g, pick[:, 1]], T).astype(np.int32) if n else np.zeros(0, np.int32)
+        AL = torch.empty(T + 1, n, self.N, device=self.eng.dev, dtype=torch.float32)      # every element is written, zero rows included
+        if n:
+            ops.beam_att_gather(self.AL_step, tb, ops.upload(pick.ravel(), torch.int32, self.eng.dev), n, G, bd, T, AL)
+        return seq, seqlp, done_beams, {"AL": AL, "len": lens}
 
 
 @torch.no_grad()
-def search_device(eng, T, opt):
-    ds = DeviceSearch(eng, T, opt)
+def search_device(eng, T, opt, return_att=False):
+    ds = DeviceSearch(eng, T, opt, return_att)
     ds.loop(fresh_tables=True)
     return ds.collect()
 
 
 @torch.no_grad()
-def search(eng, T, opt):
-    """The bookkeeping of CaptionModel.beam_search (:97-176) over an engine that owns the recurrent state."""
+def search(eng, T, opt, return_att=False):
+    """The bookkeeping of CaptionModel.beam_search (:97-176) over an engine that owns the recurrent state.
+    `return_att`: the engine also answers `attention()` ([rows, N] of the step it just ran); every kept beam gains "att" (fp32 [len, N]:
+    the attention row of the step whose logits produced each of its words, backtracked through the beam's ancestry: word 0 from the
+    <bos> step, word w >= 1 of group g from the step of loop iteration w + g - 1 at the row of the slot the beam held after word
+    w - 1), "anc" and "len", and a fourth element {"AL": numpy fp32 [T + 1, n, N], "len": int32 [n]} describes the winners."""
     beam = int(opt.get("beam_size", 10))
     G = int(opt.get("group_size", 1))
     lam = opt.get("diversity_lambda", 0.5)
@@ -324,6 +399,7 @@ def search(eng, T, opt):
         raise ValueError("beam wider than the vocabulary")
     shape = (n, G, bd, kk)
     tv, ti = (x.reshape(shape).copy() for x in eng.first(kk))
+    att_steps = [np.array(eng.attention(), np.float32)] if return_att else None     # slice 0: <bos>; slice t + 1: iteration t's step
     init = eng.snapshot() if G > 1 else None
     groups = [[_Group(T, bd) for _ in range(G)] for _ in range(n)]
     base = np.arange(rows, dtype=np.int32).reshape(n, G, bd)
@@ -342,6 +418,8 @@ def search(eng, T, opt):
                         final = {"seq": grp.seq[:, vix].copy(), "logps": grp.lps[:, vix].copy(),
                                  "unaug_p": float(grp.lps[:, vix].sum(dtype=_F32)), "p": float(grp.sums[vix])}
                         final["p"] = length_penalty(tau + 1, final["p"])
+                        if return_att:
+                            final.update(anc=grp.anc[:tau + 1, vix].copy(), len=tau + 1, rows=base[s, g].copy(), shift=g)
                         grp.done.append(final)
                         grp.sums[vix] = -1000
                 tok[s, g] = grp.seq[tau]
@@ -351,6 +429,8 @@ def search(eng, T, opt):
             eng.restore(base[:, t].reshape(-1), init)
         eng.reorder(src.reshape(-1))
         nv, ni = (x.reshape(shape) for x in eng.advance(tok.reshape(-1), kk))
+        if return_att:
+            att_steps.append(np.array(eng.attention(), np.float32))
         for g in live:
             tv[:, g], ti[:, g] = nv[:, g], ni[:, g]
     seq = torch.zeros(n, T, dtype=torch.long)
@@ -364,4 +444,13 @@ def search(eng, T, opt):
             b["seq"], b["logps"] = torch.from_numpy(b["seq"]), torch.from_numpy(b["logps"])
         done_beams.append(beams)
         seq[s], seqlp[s] = beams[0]["seq"], beams[0]["logps"]
-    return seq, seqlp, done_beams
+    if not return_att:
+        return seq, seqlp, done_beams
+    N = att_steps[0].shape[1]
+    AL, lens = np.zeros((T + 1, n, N), np.float32), np.zeros(n, np.int32)
+    for s, beams in enumerate(done_beams):
+        for b in beams:
+            rows_g, g = b.pop("rows"), b.pop("shift")
+            b["att"] = np.stack([att_steps[0][rows_g[0]]] + [att_steps[w + g][rows_g[b["anc"][w - 1]]] for w in range(1, b["len"])])
+        AL[:beams[0]["len"], s], lens[s] = beams[0]["att"], beams[0]["len"]
+    return seq, seqlp, done_beams, {"AL": AL, "len": lens}

@@ -79,6 +79,9 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
     `"grounding"`: {'subg_index', 'sort_ind', 'att2_ind', 'node_ind'} -- for the caption ranked `subg_index` (0 = best by sGPN score;
     `grd_pick[i]` = the consensus re-ranker's choice for image i, grd_utils.py:31-35) the arg-max attention column of every word
     position and the full-graph node id (= box row) it stands for (grd_utils.py:36-47; `grounding_material` finishes the entry).
+    With `beam_size > 1` (which the reference refuses for grounding, eval_utils.py:45) the entry describes the BEAM caption: the decode
+    hands over the attention of every row's winning beam (sampling.decode; subgc_beam_att_hip.h) in the same [T + 1, rows, N] layout,
+    so `grounding=`, `consensus=`, `accuracy=`, `diversity=`, `group_size > 1` and `shard=True` work as they do for a greedy decode.
 
     `consensus={"reranker": ConsensusReranker, "nn": {image_id: [nearest training-image indices]}, "top_k": 4}` (default None: off)
     re-ranks every image's sGPN-sorted captions -- its best `top_k`, None = all -- by CIDEr consensus (or, with a

@@ -294,9 +294,11 @@ class _GraphedLoop:
 class _GraphedBeam:
     """Beam search of ONE image (test.sh decodes Sub_GC_Kar with beam 2, Full-GC with beam 3) as a replayable hipGraph: with
     the candidate bookkeeping on the device (`subgc_beam_step`) the whole search is a static launch sequence, ~16 launches per
-    step on <= 10 x beam rows, i.e. launch-bound when issued eagerly."""
+    step on <= 10 x beam rows, i.e. launch-bound when issued eagerly.
+    `return_att`: the step-major attention buffer and the ancestry tables are static and filled inside the graph; the gather of the
+    winners' rows needs the host's ranking and runs after the replay, outside the graph (`DeviceSearch.collect`)."""
 
-    def __init__(self, m, n, N, P, opt, fb=None):
+    def __init__(self, m, n, N, P, opt, fb=None, return_att=False):
         dev = m.flat_params.device
         T, R, A, L = m.seq_length, m.rnn_size, m.att_hid_size, m.GCN_dim
         self.m, self.n, self.P, self.fb = m, n, P, fb
@@ -307,8 +309,8 @@ class _GraphedBeam:
             e = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)
             self.score_out, self.keep_out = e(n), z(n, dt=torch.long)
             self.ro_sel, self.h_sel, self.fc_sel, self.idx_sel = e(n, 2 * L), e(n, A), e(n, 2 * L), e(n, N, dt=torch.long)
-        self.eng = beam._BatchEngine(self.pr, P, N, int(opt.get("beam_size", 10)), m.xt_gates_table(), m.decode_snapshots())
-        self.ds = beam.DeviceSearch(self.eng, T, opt)
+        self.eng = beam._BatchEngine(self.pr, P, N, int(opt.get("beam_size", 10)), m.xt_gates_table(), m.decode_snapshots(), return_att=return_att)
+        self.ds = beam.DeviceSearch(self.eng, T, opt, return_att)
         self._loop()                                                             # eager warm-up
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
@@ -328,8 +330,9 @@ class _GraphedBeam:
         return self.ds.collect()
 
 
-def _graphed_beam(m, n, N, P, opt, fb=None):
+def _graphed_beam(m, n, N, P, opt, fb=None, return_att=False):
     okey = tuple(sorted((k, v) for k, v in opt.items() if k in ("beam_size", "group_size", "diversity_lambda", "decoding_constraint", "length_penalty")))
+    okey += (("return_att", bool(return_att)),)
     key = ("beam", n, N, okey, None if fb is None else fb.G) + m.weights_version()
     cache = m.__dict__.setdefault("_graph_cache", {})
     if key not in cache:
@@ -337,7 +340,7 @@ def _graphed_beam(m, n, N, P, opt, fb=None):
             del cache[old]
         if len(cache) >= 64:                                                      # states share their weight snapshots: a graph is a few MB
             cache.clear()
-        cache[key] = _GraphedBeam(m, n, N, P, opt, fb)
+        cache[key] = _GraphedBeam(m, n, N, P, opt, fb, return_att)
     return cache[key]
 
 
@@ -409,10 +412,15 @@ def decode_one_image(m, X2, N, image, opt, uniforms=None, forced=None):
     P = m._decoder_params()
     try:
         if beam_size > 1:
-            g = _graphed_beam(m, n, N, P, opt, fb)
-            seq, seqlp, done = g.run(None)
+            g = _graphed_beam(m, n, N, P, opt, fb, return_att)
+            res = g.run(None)
+            seq, seqlp, done = res[:3]
             m.done_beams = done
-            return (seq, seqlp, ops.copy_(torch.empty_like(g.score_out), g.score_out), ops.copy_(torch.empty_like(g.keep_out), g.keep_out))
+            r = (seq, seqlp, ops.copy_(torch.empty_like(g.score_out), g.score_out), ops.copy_(torch.empty_like(g.keep_out), g.keep_out))
+            if return_att:                                                        # [rows, steps, n_max] like the greedy path; steps = the longest beam
+                steps, n_max = int(res[3]["len"].max()), int(g.pr.lens.max().item())
+                r = r + (res[3]["AL"][:steps, :, :n_max].permute(1, 0, 2).contiguous(),)
+            return r
         k = m.the_k if m.topk_sampling else 0
         own_u = bool(k) and uniforms is None
         if own_u:
@@ -445,10 +453,15 @@ def _uniforms(m, n, T, dev):
 def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
     """Greedy / top-k / beam decode of the selected sub-graphs of one or many images as ONE batch.
     Returns one result tuple per image: (seq, seqLogprobs, score, keep[, att_weights]).
+    With beam_size > 1 and return_att, att_weights [rows, steps, n_max] holds the attention of every row's WINNING beam: entry w is the
+    distribution of the decoder step whose logits produced word w (what a teacher-forced decode along the row computes at step w),
+    zero from the row's length on; steps = the longest length among the image's rows (a length counts the end token and is T for a
+    beam cut at the last step).  Beam search never feeds its last word, so unlike the greedy path there is no T + 1-th entry.
     `batch_out` (a dict, optional): also receives the WHOLE batch's tensors in image order -- seq, seqlp, score, keep, idx (node
     lists), lens, bounds (python list of row boundaries) and, with return_att, AL (the loop's time-major attention buffer
     [T + 1, rows, N]) -- what the batched eval glue reads (eval_glue.caption_images: one ranking / grounding launch and one host copy
-    per decode batch instead of per-image tensor slicing).  `batch_out["skip_att"]`: do not cut the per-image att_weights tensors."""
+    per decode batch instead of per-image tensor slicing).  `batch_out["skip_att"]`: do not cut the per-image att_weights tensors.
+    Under beam search `seq` is a device copy of the winners' rows and AL (return_att) holds their attention, zero from a row's length on."""
     dev = X2.device
     T = m.seq_length
     return_att = opt.get("return_att", 0) == 1
@@ -475,19 +488,31 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
         graphed = None
         if len(sel) == 1 and n * beam_size <= 128 and getattr(m, "decode_hipgraph", True):
             try:
-                graphed = _graphed_beam(m, n, N, P, opt)
+                graphed = _graphed_beam(m, n, N, P, opt, return_att=return_att)
             except RuntimeError as e:                                            # capture unavailable here: same kernels, launched eagerly
                 import warnings
                 warnings.warn(f"hipGraph capture of the beam search failed ({e}); searching eagerly from now on")
                 m.decode_hipgraph = False
         if graphed is not None:
-            seq, seqlp, done = graphed.run(pr)
+            res = graphed.run(pr)
         else:
-            seq, seqlp, done = beam.beam_decode(pr, P, N, T, opt, xt_table=m.xt_gates_table())
+            res = beam.beam_decode(pr, P, N, T, opt, xt_table=m.xt_gates_table(), return_att=return_att)
+        seq, seqlp, done = res[:3]
         m.done_beams = done if len(sel) == 1 else [done[a:b] for a, b in zip(bounds, bounds[1:])]
+        AL = res[3]["AL"] if return_att else None
+        skip_att = False
         if batch_out is not None:
-            batch_out.update(_batch_view(sel, whole, seq, seqlp, None, idx_k, lens_k, bounds))
-        return [(seq[a:b], seqlp[a:b], s["score"], s["keep"]) for s, a, b in zip(sel, bounds, bounds[1:])]
+            skip_att = bool(batch_out.pop("skip_att", False))
+            view = _batch_view(sel, whole, seq, seqlp, AL, idx_k, lens_k, bounds)
+            # the glue's launches (ranking, grounding arg-max) read the token rows on the device; the search hands them back on the host
+            view["seq"] = ops.upload(seq.numpy().ravel(), torch.int64, dev).view(n, T)
+            batch_out.update(view)
+        out = [(seq[a:b], seqlp[a:b], s["score"], s["keep"]) for s, a, b in zip(sel, bounds, bounds[1:])]
+        if return_att and not skip_att:
+            h_lens, b_len = lens_k.cpu().numpy(), res[3]["len"]
+            out = [r + (AL[:int(b_len[a:b].max()), a:b, :int(h_lens[a:b].max())].permute(1, 0, 2).contiguous() if b > a else z(0, 0, 0),)
+                   for r, a, b in zip(out, bounds, bounds[1:])]
+        return out
     k = m.the_k if m.topk_sampling else 0
     own_u = bool(k) and uniforms is None and forced is None
     if own_u:

@@ -11,7 +11,7 @@ import math
 
 import torch
 
-from ._lib import SubgcError, call, call_consensus, call_criterion, call_selfcritical, lib
+from ._lib import SubgcError, call, call_beam_att, call_consensus, call_criterion, call_selfcritical, lib
 
 RELU, ACCUM = 1, 2
 FLOPS = {"on": False, "gemm": 0.0, "gemm_bytes": 0.0, "gemm_calls": 0}
@@ -1593,6 +1593,38 @@ def beam_step(tv, ti, st, tok, src, t, T, G, bd, kk, unk, constraint, lam):
          _ptr(st.sums, torch.float32), _ptr(st.done_cnt, torch.int32), _ptr(st.done_seq, torch.int32), _ptr(st.done_lps, torch.float32),
          _ptr(st.done_p, torch.float32), _ptr(st.done_len, torch.int32), _ptr(tok, torch.int64), _ptr(src, torch.int32), n, int(t), int(T),
          int(G), int(bd), int(kk), int(unk), int(bool(constraint)), float(lam), st.cap, _stream())
+
+
+BEAM_ATT_MAX_N = 4096          # SUBGC_BEAM_ATT_MAX_N
+
+
+def beam_step_anc(tv, ti, st, tok, src, t, T, G, bd, kk, unk, constraint, lam):
+    """`beam_step` that also records every beam's ancestry in st.anc / st.done_anc (subgc_beam_step_anc, subgc_beam_att_hip.h)."""
+    n = st.sums.size(0)
+    if st.anc is None or st.done_anc is None:
+        raise SubgcError("beam_step_anc: the tables were built without ancestry (DeviceTables(..., return_att=True))")
+    call_beam_att("subgc_beam_step_anc", _ptr(tv, torch.float32), _ptr(ti, torch.int32), _ptr(st.seq, torch.int32), _ptr(st.lps, torch.float32),
+                  _ptr(st.sums, torch.float32), _ptr(st.done_cnt, torch.int32), _ptr(st.done_seq, torch.int32), _ptr(st.done_lps, torch.float32),
+                  _ptr(st.done_p, torch.float32), _ptr(st.done_len, torch.int32), _ptr(st.anc, torch.int32), _ptr(st.done_anc, torch.int32),
+                  _ptr(tok, torch.int64), _ptr(src, torch.int32), n, int(t), int(T), int(G), int(bd), int(kk), int(unk), int(bool(constraint)),
+                  float(lam), st.cap, _stream())
+
+
+def beam_att_gather(al_step, st, pick, n, G, bd, T, out):
+    """out [T + 1, n, N] <- the attention rows of the finished beam pick[s] = (group, slot) of every sub-graph, zero rows behind its length
+    (subgc_beam_att_gather).  al_step [steps, n * G * bd, N] contiguous; pick int32 [n, 2] on the device, range-checked by the caller
+    (beam.check_picks)."""
+    steps, rows, N = al_step.shape
+    if not al_step.is_contiguous() or out.dim() != 3 or out.size(0) != T + 1 or out.size(1) != n or out.size(2) != N or out.stride(2) != 1:
+        raise SubgcError(f"beam_att_gather: contiguous step buffer and out [T + 1, n, N], got {tuple(al_step.shape)} and {tuple(out.shape)}")
+    if N > BEAM_ATT_MAX_N:
+        raise SubgcError(f"beam_att_gather: {N} attention columns; the limit is {BEAM_ATT_MAX_N}")
+    if pick.numel() != 2 * n:
+        raise SubgcError(f"beam_att_gather: one (group, slot) pick per sub-graph, got {pick.numel()} numbers for {n}")
+    call_beam_att("subgc_beam_att_gather", _ptr(al_step, torch.float32), al_step.stride(0), steps, rows, N, _ptr(st.done_anc, torch.int32),
+                  _ptr(st.done_len, torch.int32), _ptr(pick, torch.int32), int(n), int(G), int(bd), st.cap, int(T), _ptr(out, torch.float32),
+                  out.stride(0), out.stride(1), _stream())
+    return out
 
 
 def uniform(shape, seed, offset, device):
