@@ -17,25 +17,23 @@ import re
 import torch  # noqa: F401  (import order matters)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_hip.h")
-# the evaluation metrics are a surface of their own (subgc_accuracy_*): same library, same contract, their own header and invoker
-METRICS_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_metrics_hip.h")
-# the grounding scores (subgc_grounding_*): the third header, again with an invoker that knows only its own declarations
-GROUNDING_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_grounding_hip.h")
-# the set-controllability score (subgc_control_*): the fourth header, same arrangement
-CONTROLLABILITY_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_controllability_hip.h")
-# the label-smoothed language loss (subgc_row_lse_sum_f32, subgc_smoothed_*): the fifth header, same arrangement
-CRITERION_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_criterion_hip.h")
-# self-critical training (subgc_sc_*, subgc_reward_*): the sixth header, same arrangement
-SELFCRITICAL_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_selfcritical_hip.h")
-# consensus re-ranking, method 'bleu' (subgc_consensus_bleu_*): the seventh header, same arrangement
-CONSENSUS_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_consensus_hip.h")
-# forced decode and grounding on ground-truth sentences (subgc_forced_*, subgc_gt_grounding_*): the eighth header, same arrangement
-FORCED_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_forced_hip.h")
-# the controllability experiment's input side (subgc_sct_*): the ninth header, same arrangement
-CONTROL_INPUT_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_control_input_hip.h")
-# attention of the winning beams (subgc_beam_step_anc, subgc_beam_att_gather): the tenth header, same arrangement
-BEAM_ATT_HEADER = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "subgc_beam_att_hip.h")
+_INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
+# One surface per header: same library, same contract, an invoker that knows only its own declarations.  A new header is one entry here
+# and one `call_x = _invoker("x")` line below.
+HEADERS = {"core": "subgc_hip.h", "metrics": "subgc_metrics_hip.h", "grounding": "subgc_grounding_hip.h",
+           "controllability": "subgc_controllability_hip.h", "criterion": "subgc_criterion_hip.h", "selfcritical": "subgc_selfcritical_hip.h",
+           "consensus": "subgc_consensus_hip.h", "forced": "subgc_forced_hip.h", "control_input": "subgc_control_input_hip.h",
+           "beam_att": "subgc_beam_att_hip.h"}
+HEADER = os.path.join(_INCLUDE, HEADERS["core"])
+METRICS_HEADER = os.path.join(_INCLUDE, HEADERS["metrics"])
+GROUNDING_HEADER = os.path.join(_INCLUDE, HEADERS["grounding"])
+CONTROLLABILITY_HEADER = os.path.join(_INCLUDE, HEADERS["controllability"])
+CRITERION_HEADER = os.path.join(_INCLUDE, HEADERS["criterion"])
+SELFCRITICAL_HEADER = os.path.join(_INCLUDE, HEADERS["selfcritical"])
+CONSENSUS_HEADER = os.path.join(_INCLUDE, HEADERS["consensus"])
+FORCED_HEADER = os.path.join(_INCLUDE, HEADERS["forced"])
+CONTROL_INPUT_HEADER = os.path.join(_INCLUDE, HEADERS["control_input"])
+BEAM_ATT_HEADER = os.path.join(_INCLUDE, HEADERS["beam_att"])
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -92,7 +90,8 @@ def parse_struct(name, path=HEADER):
 
 
 _lib = None
-_protos = None
+PROTOS = {}         # key of HEADERS -> its parsed prototypes; filled once by lib()
+_protos = None      # PROTOS["core"]: what `call` checks
 
 
 def lib():
@@ -102,23 +101,16 @@ def lib():
             raise SubgcError(f"{LIB_PATH} is missing: run `python sub-gc_amd/build.py` (hipcc, gfx950). "
                              "There is no CPU fallback for the Sub-GC hot path.")
         L = ctypes.CDLL(LIB_PATH)
-        _protos = parse_header()
-        for hdr, protos in (("subgc_hip.h", _protos), ("subgc_metrics_hip.h", parse_header(METRICS_HEADER)),
-                            ("subgc_grounding_hip.h", parse_header(GROUNDING_HEADER)),
-                            ("subgc_controllability_hip.h", parse_header(CONTROLLABILITY_HEADER)),
-                            ("subgc_criterion_hip.h", parse_header(CRITERION_HEADER)),
-                            ("subgc_selfcritical_hip.h", parse_header(SELFCRITICAL_HEADER)),
-                            ("subgc_consensus_hip.h", parse_header(CONSENSUS_HEADER)),
-                            ("subgc_forced_hip.h", parse_header(FORCED_HEADER)),
-                            ("subgc_control_input_hip.h", parse_header(CONTROL_INPUT_HEADER)),
-                            ("subgc_beam_att_hip.h", parse_header(BEAM_ATT_HEADER))):
-            for name, (ret, args) in protos.items():
+        for key, hdr in HEADERS.items():
+            PROTOS[key] = parse_header(os.path.join(_INCLUDE, hdr))
+            for name, (ret, args) in PROTOS[key].items():
                 try:
                     fn = getattr(L, name)
                 except AttributeError as e:
                     raise SubgcError(f"libsubgc_hip.so does not export {name} declared in {hdr}") from e
                 fn.restype = ret
                 fn.argtypes = [a for a, _ in args]
+        _protos = PROTOS["core"]
         if L.subgc_version() != 1:
             raise SubgcError("libsubgc_hip.so ABI version mismatch")
         _lib = L
@@ -141,66 +133,33 @@ def call(name, *args):
         raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
 
 
-def _call_in(header, cache, name, args):
-    """`call` for the entry points of one of the other headers: a cache per header, so that no invoker reaches another's declarations."""
-    fn = cache.get(name)
-    if fn is None:
-        if name not in parse_header(header):
-            raise SubgcError(f"{name} is not declared in {os.path.basename(header)}")
-        fn = cache[name] = getattr(lib(), name)
-    rc = fn(*args)
-    if rc != 0:
-        raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
+def _invoker(key):
+    """`call` for the entry points of one header of HEADERS: a cache of its own, so that no invoker reaches another's declarations."""
+    cache, hdr = {}, HEADERS[key]
+
+    def invoke(name, *args):
+        fn = cache.get(name)
+        if fn is None:
+            L = lib()
+            if name not in PROTOS[key]:
+                raise SubgcError(f"{name} is not declared in {hdr}")
+            fn = cache[name] = getattr(L, name)
+        rc = fn(*args)
+        if rc != 0:
+            raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
+
+    return invoke
 
 
-_FN_METRICS, _FN_GROUNDING, _FN_CONTROLLABILITY, _FN_CRITERION, _FN_SELFCRITICAL, _FN_CONSENSUS = {}, {}, {}, {}, {}, {}
-_FN_FORCED, _FN_CONTROL_INPUT, _FN_BEAM_ATT = {}, {}, {}
-
-
-def call_metrics(name, *args):
-    """`call` for the entry points of subgc_metrics_hip.h."""
-    _call_in(METRICS_HEADER, _FN_METRICS, name, args)
-
-
-def call_grounding(name, *args):
-    """`call` for the entry points of subgc_grounding_hip.h."""
-    _call_in(GROUNDING_HEADER, _FN_GROUNDING, name, args)
-
-
-def call_controllability(name, *args):
-    """`call` for the entry points of subgc_controllability_hip.h."""
-    _call_in(CONTROLLABILITY_HEADER, _FN_CONTROLLABILITY, name, args)
-
-
-def call_criterion(name, *args):
-    """`call` for the entry points of subgc_criterion_hip.h."""
-    _call_in(CRITERION_HEADER, _FN_CRITERION, name, args)
-
-
-def call_selfcritical(name, *args):
-    """`call` for the entry points of subgc_selfcritical_hip.h."""
-    _call_in(SELFCRITICAL_HEADER, _FN_SELFCRITICAL, name, args)
-
-
-def call_consensus(name, *args):
-    """`call` for the entry points of subgc_consensus_hip.h."""
-    _call_in(CONSENSUS_HEADER, _FN_CONSENSUS, name, args)
-
-
-def call_forced(name, *args):
-    """`call` for the entry points of subgc_forced_hip.h."""
-    _call_in(FORCED_HEADER, _FN_FORCED, name, args)
-
-
-def call_control_input(name, *args):
-    """`call` for the entry points of subgc_control_input_hip.h."""
-    _call_in(CONTROL_INPUT_HEADER, _FN_CONTROL_INPUT, name, args)
-
-
-def call_beam_att(name, *args):
-    """`call` for the entry points of subgc_beam_att_hip.h."""
-    _call_in(BEAM_ATT_HEADER, _FN_BEAM_ATT, name, args)
-
+call_metrics = _invoker("metrics")
+call_grounding = _invoker("grounding")
+call_controllability = _invoker("controllability")
+call_criterion = _invoker("criterion")
+call_selfcritical = _invoker("selfcritical")
+call_consensus = _invoker("consensus")
+call_forced = _invoker("forced")
+call_control_input = _invoker("control_input")
+call_beam_att = _invoker("beam_att")
 
 FAM = {"gemm": 1, "attn": 2, "lstm": 3, "gcn": 4, "pool": 5, "softmax": 6}
 

@@ -26,9 +26,10 @@ import math
 
 import numpy as np
 
+from . import _scoring
 from ._lib import SubgcError, call_metrics
+from ._scoring import MAX_IDS
 
-MAX_IDS = 65535          # word ids 1 .. 65535 (16-bit lanes of the n-gram key; 0 = no word)
 MAX_T = 64               # words of a candidate row
 MAX_REF_WORDS = 256      # words of a reference caption (SUBGC_ACC_MAX_REF_WORDS)
 MAX_REFS = 32            # reference captions of an image (SUBGC_ACC_MAX_REFS)
@@ -94,11 +95,8 @@ class AccuracyReferences:
         self.ukeys, self.ulogdf, self.ref_len, self.gauss, self.bad = c.ukeys, c.ulogdf, c.ref_len, c.gauss, c.bad
         self.boff, self.bkeys, self.bmax = bleu_table(self.words, self.woff, self.cap_off)
         self.device = None
-        if device == "auto":
-            import torch
-            device = torch.device("cuda", torch.cuda.current_device())
         if device is not None:
-            self.to(device)
+            self.to(_scoring.resolve_device(device))
 
     def to(self, device):
         """Upload the tables and cook every reference caption (one launch); done once."""
@@ -138,11 +136,7 @@ class AccuracyScorer:
         return 2 * (ROW_F64 * rows + IMG_F64 * I) + ROW_INT * rows + IMG_INT * I
 
     def check_index(self, image_index):
-        idx = [int(x) for x in image_index]
-        for i, j in enumerate(idx):
-            if not 0 <= j < self.refs.n_img:
-                raise SubgcError(f"accuracy: batch image {i} names reference image {j}; the references hold {self.refs.n_img} images")
-        return idx
+        return _scoring.check_index("accuracy", image_index, self.refs.n_img)
 
     def enqueue(self, seq, seg, I, d_index, first, remove_bad_endings, arena, oracle=True):
         """The cook launch and the two accuracy launches on the current stream (`oracle=False`: the row records alone, without the per-image
@@ -154,11 +148,8 @@ class AccuracyScorer:
         r = self.refs
         if r.device is None:
             raise SubgcError("accuracy: the references are not on a device (AccuracyReferences(..., device=...) or .to(device))")
-        if seq.dtype not in (torch.int32, torch.int64) or not seq.is_contiguous() or seq.dim() != 2:
-            raise SubgcError(f"accuracy: contiguous int32 / int64 token rows [rows, T], got {seq.dtype} {tuple(seq.shape)}")
-        rows, T = seq.shape
-        if T > MAX_T:
-            raise SubgcError(f"accuracy: token rows of {T} words; the limit is {MAX_T}")
+        t64, T = _scoring.token_rows("accuracy", seq, MAX_T)
+        rows = seq.size(0)
         if arena.numel() < self.arena_words(rows, I) or arena.data_ptr() % 8:
             raise SubgcError("accuracy: the result arena is too short or not 8-byte aligned")
         c = r.corpus
@@ -167,7 +158,7 @@ class AccuracyScorer:
         ck, cw, cc, cl, cn = ops.consensus_cook(seq, c.d_ukeys, c.d_ulogdf, c.ref_len, bad=bad)
         rk, rw, rc, rl, rn = c.cooked
         P, s = ops._ptr, ops._stream()
-        call_metrics("subgc_accuracy_rows", P(seq), int(seq.dtype == torch.int64), int(T), P(bad, torch.uint8), 0 if bad is None else bad.numel(),
+        call_metrics("subgc_accuracy_rows", P(seq), t64, int(T), P(bad, torch.uint8), 0 if bad is None else bad.numel(),
                      int(rows), P(seg, torch.int32), int(I), P(d_index, torch.int32), r.n_img, P(ck, torch.int64), P(cw, torch.float64),
                      P(cc, torch.int32), P(cl, torch.int32), P(cn, torch.float64), P(c.d_cap_off, torch.int32), r.n_caps,
                      P(c.d_woff, torch.int32), P(r.d_words, torch.int32), len(r.words), P(rk, torch.int64), P(rw, torch.float64),
@@ -182,12 +173,28 @@ class AccuracyScorer:
     @staticmethod
     def views(arena, rows, I):
         """(row fp64 [rows, 6], row int32 [rows, 10], image fp64 [I, 12], image int32 [I, 56]) views of an arena (torch or numpy)."""
-        f64 = np.float64 if isinstance(arena, np.ndarray) else __import__("torch").float64
+        f64 = _scoring.dtypes(arena).float64
         n_d = 2 * (ROW_F64 * rows + IMG_F64 * I)
         d = arena[:n_d].view(f64)
         i0 = n_d + ROW_INT * rows
         return (d[:ROW_F64 * rows].reshape(rows, ROW_F64), arena[n_d:i0].reshape(rows, ROW_INT), d[ROW_F64 * rows:].reshape(I, IMG_F64),
                 arena[i0:i0 + IMG_INT * I].reshape(I, IMG_INT))
+
+    def batch_pass(self, arg, batch, slots):
+        """The accuracy pass of `eval_collect` (arg: its `accuracy=`): the images' reference indices go up with the batch; the top-1 row
+        is `batch.c_first` (the consensus pass's first choice) when there is one, row 0 otherwise."""
+        rows, I = batch.rows, batch.I
+        index = self.check_index(arg["index"])
+        if len(index) != I:
+            raise SubgcError("eval_collect: accuracy needs one reference-image index per image")
+        n = self.arena_words(rows, I)
+        s_index, w, live = slots.ints(index), slots.words(n, align8=True), bool(I and rows)
+
+        def enqueue():
+            if live:
+                self.enqueue(batch.seq_s, batch.seg, I, slots.seg[s_index], batch.c_first, arg.get("remove_bad_endings", 0), slots.arena[w])
+
+        return enqueue, lambda host: {"a_words": host[w].copy() if live else np.zeros(n, np.int32)}
 
     def unpack(self, host, bounds):
         """The host copy of an arena -> per image a dict of plain numpy data:
@@ -228,6 +235,14 @@ class AccuracyScorer:
         arena = torch.empty(max(words, 2), device=dev, dtype=torch.int32)
         self.enqueue(seq.contiguous(), tab, I, tab[I + 1:2 * I + 1], None if first is None else tab[2 * I + 1:], remove_bad_endings, arena)
         return self.unpack(arena.cpu().numpy(), bounds)                      # the one copy
+
+
+def chunk_entries(arg, h, bounds):
+    """`caption_images(accuracy=...)`: what every image's entry gains from `eval_collect`'s outputs `h` (None: a batch without rows, every image the entry of no captions)."""
+    sc = arg["scorer"]
+    if h is None:
+        return [{"accuracy": sc.unpack(np.zeros(sc.arena_words(0, 1), np.int32), [0, 0])[0]} for _ in bounds[1:]]
+    return [{"accuracy": e} for e in sc.unpack(h["a_words"], bounds)]
 
 
 def corpus_bleu(material):
@@ -279,13 +294,7 @@ def encode_predictions(predictions, refs):
             except SubgcError as e:
                 raise SubgcError(f"{e} (a caption of image {p.get('image_id')!r})") from None
         bounds.append(len(rows))
-    T = max([len(r) for r in rows] + [1])
-    if T > MAX_T:
-        raise SubgcError(f"accuracy: a caption of {T} words; the limit is {MAX_T}")
-    seq = np.zeros((len(rows), T), np.int64)
-    for r, ids in enumerate(rows):
-        seq[r, :len(ids)] = ids
-    return seq, bounds
+    return _scoring.id_rows("accuracy", rows, MAX_T), bounds
 
 
 def score_predictions(predictions, refs, ix_to_word, oracle_num=1, remove_bad_endings=0, device="auto", verbose=True):
@@ -302,7 +311,7 @@ def score_predictions(predictions, refs, ix_to_word, oracle_num=1, remove_bad_en
         refs = AccuracyReferences([refs[p["image_id"]] for p in predictions], ix_to_word, device=None)
     if refs.n_img != len(predictions):
         raise SubgcError(f"accuracy: {len(predictions)} images predicted, the references hold {refs.n_img}")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device == "auto" else torch.device(device)
+    dev = _scoring.resolve_device(device)
     if refs.device is None:
         refs.to(dev)
     seq, bounds = encode_predictions(predictions, refs)

@@ -24,8 +24,8 @@ import torch
 
 from . import ops
 from ._lib import SubgcError
+from ._scoring import MAX_IDS, bad_table, resolve_device
 
-MAX_IDS = 65535          # word ids 1 .. 65535 (16-bit lanes of the n-gram key; 0 = no word)
 MAX_WORDS = 256          # words of one corpus caption (subgc_consensus_cook)
 MAX_CAPS = 2048          # neighbour captions per image (subgc_consensus_score)
 MAX_K = 256              # neighbour images per image
@@ -124,18 +124,11 @@ class ConsensusCorpus:
         self.ulogdf = np.log(np.maximum(1.0, df.astype(np.float64)))
         self.ref_len = float(np.log(float(self.n_img)))
         self.gauss = gauss_table(MAX_WORDS, sigma)
-        bad = np.zeros(max((int(k) for k in ix_to_word), default=0) + 1, np.uint8)
-        from .eval_glue import BAD_ENDINGS
-        for k, w in ix_to_word.items():
-            if w in BAD_ENDINGS:
-                bad[int(k)] = 1
-        self.bad = bad
+        self.bad = bad_table(ix_to_word)
         self.device = None
         self._bleu_cooked = None
-        if device == "auto":
-            device = torch.device("cuda", torch.cuda.current_device())
         if device is not None:
-            self.to(device)
+            self.to(resolve_device(device))
 
     def to(self, device):
         """Upload the tables and cook every corpus caption (one launch); done once."""
@@ -189,7 +182,7 @@ class ConsensusReranker:
         for j, l in enumerate(nn_lists):
             if len(l) < k:
                 raise SubgcError(f"consensus: k = {k} is larger than the neighbour list of image {j} ({len(l)} entries)")
-        nn = np.asarray([np.asarray(l[:k], np.int64) for l in nn_lists], np.int64).reshape(len(nn_lists), k)
+        nn = np.asarray([l[:k] for l in nn_lists], np.int64).reshape(len(nn_lists), k)             # one conversion for the batch
         cl = np.clip(nn, 0, c.n_img - 1)                                    # what the kernel reads for an index out of range
         caps = (c.cap_off[cl + 1] - c.cap_off[cl]).sum(1)
         max_caps = int(caps.max()) if len(caps) else 0
@@ -221,6 +214,20 @@ class ConsensusReranker:
         cand = ops.consensus_cook(seq, c.d_ukeys, c.d_ulogdf, c.ref_len, bad=c.d_bad if remove_bad_endings else None)
         ops.consensus_score(cand, T, seg, I, max_rows, top_k, d_nn, self.k, c.d_cap_off, c.n_img, c.n_caps, c.d_woff, c.cooked, c.d_gauss,
                             self.m, max_caps, sim, pair_out)
+
+    def batch_pass(self, arg, batch, slots):
+        """The consensus pass of `eval_collect` (arg: its `consensus=`): fp64 sums | order | first choice in the batch's arena; publishes
+        `batch.c_first`, the device int32 [I] first choices, for the accuracy and grounding passes."""
+        rows, I = batch.rows, batch.I
+        w_sim, w_order, w_first = slots.words(2 * rows, align8=True), slots.words(rows), slots.words(I)
+
+        def enqueue():
+            batch.c_first = slots.arena[w_first]
+            if I and rows:
+                self.enqueue(batch.seq_s, batch.seg, I, batch.max_rows, arg["nn"], arg.get("top_k"), arg.get("remove_bad_endings", 0),
+                             slots.arena[w_sim].view(torch.float64), slots.arena[w_order], batch.c_first)
+
+        return enqueue, lambda host: {"c_sim": host[w_sim].view(np.float64).copy(), "c_order": host[w_order].copy(), "c_first": host[w_first].copy()}
 
     def rerank(self, seq, bounds, nn_lists, top_k=None, remove_bad_endings=0, return_pairs=False):
         """seq [rows, T]: the decode batch's device token rows, image i owning rows bounds[i] .. bounds[i+1]-1 in sGPN-ranked order;
@@ -287,6 +294,15 @@ def make_reranker(corpus, method="cider", **kw):
     if method == "bleu":
         return BleuConsensusReranker(corpus, **kw)
     raise SubgcError(f"consensus: method = {method!r}; only support cider and bleu currently")      # consensus_reranking.py:123-124
+
+
+def chunk_entries(arg, h, bounds):
+    """`caption_images(consensus=...)`: what every image's entry gains from `eval_collect`'s outputs `h` (None: a batch without rows)."""
+    if h is None:
+        return [{"consensus_rerank_ind": np.zeros(0, np.int64), "consensus_sim": np.zeros(0, np.float64)} for _ in bounds[1:]]
+    k = arg.get("top_k")
+    keep = [(b - a) if not k else min(b - a, int(k)) for a, b in zip(bounds, bounds[1:])]
+    return [{"consensus_rerank_ind": h["c_order"][a:a + n].astype(np.int64), "consensus_sim": h["c_sim"][a:a + n].copy()} for a, n in zip(bounds, keep)]
 
 
 def _ngram_counters(ids):

@@ -20,8 +20,9 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import accuracy as _accuracy
+from . import _scoring, accuracy as _accuracy
 from ._lib import SubgcError, call_controllability
+from ._scoring import csr as _csr
 
 MAX_WORDS = 64           # SUBGC_CTL_MAX_WORDS: vector words of a caption, on either side
 COS_EPS = 1e-8           # the clamp of the cosine's denominator
@@ -56,11 +57,8 @@ class NounVectors:
         for k, w in ix_to_word.items():
             self.tok_noun[int(k)] = self.word_row.get(w, -1)
         self.device = None
-        if device == "auto":
-            import torch
-            device = torch.device("cuda", torch.cuda.current_device())
         if device is not None:
-            self.to(device)
+            self.to(_scoring.resolve_device(device))
 
     def to(self, device):
         import torch
@@ -68,10 +66,6 @@ class NounVectors:
         self.d_vec, self.d_norm = torch.from_numpy(self.vec).to(dev), torch.from_numpy(self.norm).to(dev)
         self.device = dev
         return self
-
-
-def _csr(counts):
-    return np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64))]).astype(np.int64)
 
 
 class ControlReferences:
@@ -105,11 +99,8 @@ class ControlReferences:
         for w, k in self.accuracy.word_to_ix.items():
             self.tok_noun[k] = nouns.word_row.get(w, -1)
         self.device = None
-        if device == "auto":
-            import torch
-            device = torch.device("cuda", torch.cuda.current_device())
         if device is not None:
-            self.to(device)
+            self.to(_scoring.resolve_device(device))
 
     def to(self, device):
         """Upload the tables (the vectors too, if they are not there yet); done once."""
@@ -154,11 +145,7 @@ class ControlScorer:
 
     def views(self, arena, plan):
         """(accuracy arena, iou fp32 [rows], pair_iou fp32 [P], pair_mn int32 [P, 2], assign int8 [P, 64]) views of an arena (torch or numpy)."""
-        if isinstance(arena, np.ndarray):
-            f32, i8 = np.float32, np.int8
-        else:
-            import torch
-            f32, i8 = torch.float32, torch.int8
+        f32, i8 = (ns := _scoring.dtypes(arena)).float32, ns.int8
         rows, P = plan["rows"], plan["P"]
         o = self.acc.arena_words(rows, rows)
         acc = arena[:o]
@@ -176,9 +163,8 @@ class ControlScorer:
         r, nv = self.refs, self.refs.nouns
         if r.device is None:
             raise SubgcError("controllability: the references are not on a device (ControlReferences(..., device=...) or .to(device))")
-        if seq.dtype not in (torch.int32, torch.int64) or not seq.is_contiguous() or seq.dim() != 2:
-            raise SubgcError(f"controllability: contiguous int32 / int64 token rows [rows, T], got {seq.dtype} {tuple(seq.shape)}")
-        rows, T = seq.shape
+        t64, T = _scoring.token_rows("controllability", seq)
+        rows = seq.size(0)
         if rows != plan["rows"]:
             raise SubgcError(f"controllability: {rows} token rows, the plan holds {plan['rows']}")
         if arena.numel() < self.arena_words(plan):
@@ -186,7 +172,7 @@ class ControlScorer:
         _, iou, pair, mn, ass = self.views(arena, plan)
         bad = r.accuracy.corpus.d_bad if remove_bad_endings else None
         P, has = ops._ptr, plan["P"] > 0
-        call_controllability("subgc_control_noun_iou", P(seq), int(seq.dtype == torch.int64), int(T), P(bad, torch.uint8), 0 if bad is None else bad.numel(),
+        call_controllability("subgc_control_noun_iou", P(seq), t64, int(T), P(bad, torch.uint8), 0 if bad is None else bad.numel(),
                              int(rows), P(r.d_tok_noun, torch.int32), len(r.tok_noun), P(nv.d_vec, torch.float32), P(nv.d_norm, torch.float64), nv.n_noun,
                              nv.d, P(table[:rows], torch.int32), r.n_groups, P(table[rows:2 * rows + 1], torch.int32), plan["P"],
                              P(r.d_gcap_off, torch.int32), r.n_caps, P(r.d_gn_off, torch.int32), P(r.d_gn, torch.int32), r.n_gn,
@@ -273,7 +259,7 @@ def score_predictions(predictions, order_list, refs, ix_to_word, remove_bad_endi
     caps, ids = order_captions(predictions, order_list)
     if len(caps) != refs.n_groups:
         raise ValueError(f"controllability: {len(caps)} generated captions, the references hold {refs.n_groups} groups")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device == "auto" else torch.device(device)
+    dev = _scoring.resolve_device(device)
     if refs.device is None:
         refs.to(dev)
     rows = []
@@ -282,12 +268,7 @@ def score_predictions(predictions, order_list, refs, ix_to_word, remove_bad_endi
             rows.append(refs.accuracy.encode(c))
         except SubgcError as e:
             raise SubgcError(f"{e} (a caption of image {img!r})") from None
-    T = max([len(r) for r in rows] + [1])
-    if T > MAX_WORDS:
-        raise SubgcError(f"controllability: a caption of {T} words; the limit is {MAX_WORDS}")
-    seq = np.zeros((len(rows), T), np.int64)
-    for r, ids_ in enumerate(rows):
-        seq[r, :len(ids_)] = ids_
+    seq = _scoring.id_rows("controllability", rows, MAX_WORDS)
     entries = ControlScorer(refs).score(torch.from_numpy(seq).to(dev), list(range(len(rows))), remove_bad_endings=remove_bad_endings)
     s = summarize(entries)
     if verbose:

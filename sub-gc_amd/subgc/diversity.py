@@ -34,8 +34,8 @@ import hashlib
 import numpy as np
 
 from ._lib import SubgcError
+from ._scoring import MAX_IDS, bad_table, id_rows, resolve_device
 
-MAX_IDS = 65535          # word ids 1 .. 65535 (16-bit lanes of the n-gram key; 0 = no word)
 MAX_DRAW = 1024          # rows of one draw
 MAX_T = 64               # words of a token row
 METRICS = (4, 3, 2, 1)   # the script's order
@@ -84,15 +84,6 @@ def _inverse_vocab(ix_to_word):
     return w2i
 
 
-def _bad_table(ix_to_word):
-    from .eval_glue import BAD_ENDINGS
-    bad = np.zeros(max((int(k) for k in ix_to_word), default=0) + 1, np.uint8)
-    for k, w in ix_to_word.items():
-        if w in BAD_ENDINGS:
-            bad[int(k)] = 1
-    return bad
-
-
 class NoveltyIndex:
     """The set of training captions (diversity_score.py:127-131) as distinct id lists in lexicographic order (a prefix first), CSR;
     see the module docstring for what is kept and dropped.  `.captions`: the kept id tuples, `.dropped`: how many strings were dropped.
@@ -119,11 +110,8 @@ class NoveltyIndex:
             raise SubgcError("diversity: the training captions hold 2^31 words or more")
         self.tok = np.asarray([w for c in order for w in c], np.int32)
         self.device = None
-        if device == "auto":
-            import torch
-            device = torch.device("cuda", torch.cuda.current_device())
         if device is not None:
-            self.to(device)
+            self.to(resolve_device(device))
 
     def to(self, device):
         import torch
@@ -170,7 +158,7 @@ class DiversityScorer:
             raise SubgcError(f"diversity: n_best = {n_best}; 2 <= n_best <= 16")
         self.novelty, self.n_best = novelty, int(n_best)
         vocab = ix_to_word if ix_to_word is not None else (novelty.ix_to_word if novelty is not None else None)
-        self.bad = None if vocab is None else _bad_table(vocab)
+        self.bad = None if vocab is None else bad_table(vocab)
         self._d_bad = None
 
     def plan(self, draws, sizes):
@@ -227,6 +215,20 @@ class DiversityScorer:
         ops.diversity_distinct(seq, bad, seg, I, set_img, set_off, set_flags, draw, S, plan["n_draw"], plan["max_draw"], out_i)
         ops.diversity_best(seq, bad, seg, I, set_img, set_flags, S, self.n_best, None if nv is None else nv.d_off,
                            None if nv is None else nv.d_tok, 0 if nv is None else nv.n, out_i, out_d)
+
+    def batch_pass(self, arg, batch, slots):
+        """The diversity pass of `eval_collect` (arg: its `diversity=`): the sets' fp64 values, then their integer columns."""
+        import torch
+        from .ops import DIV_COLS
+        plan, S, nb = arg["plan"], arg["plan"]["n_sets"], self.n_best
+        w_d, w_i = slots.words(2 * S * (nb + 1), align8=True), slots.words(S * (DIV_COLS + nb))
+
+        def enqueue():
+            if S:
+                self.enqueue(batch.seq_s, batch.score_s, batch.seg, batch.I, plan, arg.get("remove_bad_endings", 0),
+                             slots.arena[w_i].view(S, DIV_COLS + nb), slots.arena[w_d].view(torch.float64).view(S, nb + 1))
+
+        return enqueue, lambda host: {"d_f64": host[w_d].view(np.float64).reshape(S, nb + 1).copy(), "d_int": host[w_i].reshape(S, DIV_COLS + nb).copy()}
 
     def unpack(self, plan, h_int, h_f64, top_n=None):
         """Host results of a plan -> per image {"drawn", "distinct" (metric 1), "words", "unigrams", "bigrams" (3), "novel", "novel_of" (2:
@@ -292,6 +294,21 @@ class DiversityScorer:
         return self.unpack(plan, host[n_f64:].reshape(S, ops.DIV_COLS + nb), host[:n_f64].view(np.float64).reshape(S, nb + 1))
 
 
+def chunk_arg(arg, opt, ids, sizes):
+    """`caption_images(diversity=opt)`: the chunk's argument with the plan of its draws, which are keyed by the image id
+    (`per_image_draws`); "top_n" rides along for `chunk_entries`."""
+    top_n = tuple(opt.get("top_n", TOP_N))
+    return dict(arg, top_n=top_n, plan=opt["scorer"].plan(per_image_draws(sizes, ids, top_n, opt.get("seed", 2019)), sizes))
+
+
+def chunk_entries(arg, h, bounds):
+    """What every image's entry gains from `eval_collect`'s outputs `h` (None: a batch without rows, all counts zero)."""
+    from .ops import DIV_COLS
+    sc, S = arg["scorer"], arg["plan"]["n_sets"]
+    d_int, d_f64 = (np.zeros((S, DIV_COLS + sc.n_best), np.int32), np.zeros((S, sc.n_best + 1))) if h is None else (h["d_int"], h["d_f64"])
+    return [{"diversity": e} for e in sc.unpack(arg["plan"], d_int, d_f64, arg["top_n"])]
+
+
 def summarize(per_image):
     """The per-image entries of `DiversityScorer.score` (or the `"diversity"` entries of `caption_images`) -> the numbers the script
     prints, each a list with one value per top_n: "mbleu4" (:81-82; the mean over the images with a valid value, "mbleu4_left_out" counts
@@ -347,13 +364,7 @@ def encode_predictions(predictions, ix_to_word):
                 raise SubgcError(f"diversity: word {e.args[0]!r} of a caption of image {p.get('image_id')!r} is not in the vocabulary") from None
         scores.append(sc)
         bounds.append(len(rows))
-    T = max([len(r) for r in rows] + [1])
-    if T > MAX_T:
-        raise SubgcError(f"diversity: a caption of {T} words; the limit is {MAX_T}")
-    seq = np.zeros((len(rows), T), np.int64)
-    for r, ids in enumerate(rows):
-        seq[r, :len(ids)] = ids
-    return seq, bounds, (np.concatenate(scores) if scores else np.zeros(0, np.float32))
+    return id_rows("diversity", rows, MAX_T), bounds, (np.concatenate(scores) if scores else np.zeros(0, np.float32))
 
 
 def score_predictions(predictions, ix_to_word, novelty=None, evaluate_mB4=False, top_n=TOP_N, seed=2019, n_best=5, device="auto"):
@@ -361,7 +372,7 @@ def score_predictions(predictions, ix_to_word, novelty=None, evaluate_mB4=False,
     the script's own draws (`reference_draws`), one scoring pass on the device.  -> (summarize(...), the per-image entries)."""
     import torch
     seq, bounds, score = encode_predictions(predictions, ix_to_word)
-    dev = torch.device("cuda", torch.cuda.current_device()) if device == "auto" else torch.device(device)
+    dev = resolve_device(device)
     draws = reference_draws([b - a for a, b in zip(bounds, bounds[1:])], top_n, evaluate_mB4, seed)
     scorer = DiversityScorer(novelty, n_best, ix_to_word=ix_to_word)
     per_image = scorer.score(torch.from_numpy(seq).to(dev), bounds, torch.from_numpy(score).to(dev), draws)

@@ -7,17 +7,20 @@ map the kept sub-graphs back to their original indices, turn token rows into sen
 the chosen caption the graph node with the largest attention weight.  Here the model call is `sample_images`
 (many images per decode batch); ranking, reordering and the grounding arg-max are ONE launch each over the whole
 batch (`subgc_eval_rank_rows`, `subgc_grounding_argmax`) and everything the host needs arrives in ONE copy per
-decode batch (`ops.eval_collect`).  The text side of the grounding protocol (lemma -> detection class, box files:
+decode batch (`eval_collect`: a fixed sequence of passes over one int32 upload and one int32 result arena; every optional scorer has a
+`batch_pass` beside its own code).  The text side of the grounding protocol (lemma -> detection class, box files:
 `grounding_material`) is dictionary look-ups on the host; the COCO / GVD metric scripts are out of scope.
 """
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from . import ops
+from ._lib import SubgcError, call
 
 # misc/utils.py:16-17
 BAD_ENDINGS = ("with", "in", "on", "of", "a", "at", "to", "for", "an", "this", "his", "her", "that", "the")
@@ -49,6 +52,27 @@ def decode_sequence(ix_to_word, seq, remove_bad_endings=None):
     return out
 
 
+# One description per option of `caption_images`, the first four in eval_collect's pass order.  only_sct: defined only in sct mode (else:
+# not there); att: needs return_att and the attention buffer; covers: its id-keyed dicts that must hold every image, lacks: what a gap in
+# them is called; what + verbs: the subject of its refusals.  A chunk's list-keyed argument is the option with those dicts read at the
+# chunk's ids, finished by the scorer module's `chunk_arg` where it says so (per-image draws, prepared boxes); what an image of a row-less
+# batch gets and which entry keys are attached is the module's `chunk_entries`.  Controllability is scored per image
+# (`_score_controllability`).
+_OPTIONS = {
+    "consensus": dict(only_sct=False, att=False, covers=("nn",), lacks="consensus['nn'] has no neighbour list", what="consensus re-ranking",
+                      verbs=("is", "needs")),
+    "diversity": dict(only_sct=False, att=False, covers=(), lacks="", what="diversity scores", verbs=("are", "need"), chunk_arg=True),
+    "accuracy": dict(only_sct=False, att=False, covers=("index",), lacks="accuracy['index'] names no reference image", what="accuracy scores",
+                     verbs=("are", "need")),
+    "grounding": dict(only_sct=False, att=True, covers=("index", "boxes"), lacks="grounding['index'] / ['boxes'] name no reference image or no boxes",
+                      what="grounding scores", verbs=("are", "need"), chunk_arg=True),
+    "controllability": dict(only_sct=True, att=False, covers=("index",), lacks="controllability['index'] names no first group",
+                            what="controllability scores", verbs=("are", "need")),
+}
+_NOT_IN_SCT = "not defined in sct (controllability) mode: its captions keep the input order and are not ranked"
+_ONLY_SCT = "defined only in sct (controllability) mode (eval_kwargs['sct'] = 1): they need one caption per input region set, in input order"
+
+
 def rank_subgraphs(model, seqq, subgraph_score, keep_nms_ind, sct_mode=False):
     """eval_utils.py:105-121 -> (seq, subgraph_score, sorted_subgraph_ind, sort_ind)."""
     if sct_mode:                                                          # controllability: input order, first half only
@@ -59,6 +83,106 @@ def rank_subgraphs(model, seqq, subgraph_score, keep_nms_ind, sct_mode=False):
         return seqq[sort_ind.to(seqq.device)], sorted_score, keep_nms_ind[sort_ind], sort_ind
     sort_ind = torch.arange(subgraph_score.size(0), device=keep_nms_ind.device).type_as(keep_nms_ind)
     return seqq, subgraph_score, keep_nms_ind, sort_ind
+
+
+class Slots:
+    """Two-phase reservation for `eval_collect`: `ints` / `words` hand out slices while the passes are set up; then `seg` is the single upload
+    of `values` and `arena` the single int32 result tensor of `n_words` they index; the same slices index the arena's one host copy."""
+
+    def __init__(self, values):
+        self.values, self.n_words = values, 0
+
+    def ints(self, values):
+        a = len(self.values)
+        self.values += values
+        return slice(a, len(self.values))
+
+    def words(self, n, align8=False):
+        a = (self.n_words + 1) & ~1 if align8 else self.n_words        # an fp64 slot starts 8-byte aligned
+        self.n_words = a + n
+        return slice(a, self.n_words)
+
+
+def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pick=None, consensus=None, diversity=None, accuracy=None,
+                 grounding=None):
+    """The eval loop's per-image work for a whole decode batch (misc/eval_utils.py:105-121; grounding: misc/grd_utils.py:36-47):
+    one ranking launch (subgc_eval_rank_rows), one grounding launch when `AL` (the decode loop's attention buffer [T1, rows, N]) and
+    `idx` (the kept sub-graphs' node lists [rows, N]) are given, and ONE device -> host copy of everything.
+    score [rows] fp32, keep [rows] int64, seq [rows, T] int64, bounds: python list of the I + 1 row boundaries of the images,
+    pick: optional per-image subg_index list (default 0 = the best-ranked caption).
+    consensus: optional {"reranker": ConsensusReranker, "nn": per-image neighbour index lists, "top_k": int or None, "remove_bad_endings": 0 / 1}:
+    the ranked token rows are re-ranked on the device in the same pass (subgc_consensus_cook / _score / _rank) and, unless `pick` is
+    given, the grounding launch takes each image's pick from the re-ranker's first choice ON THE DEVICE; its outputs ride in the same copy.
+    -> dict of host numpy arrays: order / score / keep (int64) / seq (int64) [rows...], and with grounding att2 / node [I, T1], n_words [I];
+    with consensus c_order (int32 [rows]: image i's order in its first n_i' = min(n_i, top_k) slots), c_sim (fp64 [rows]), c_first [I].
+    diversity: optional {"scorer": DiversityScorer, "plan": its `plan(draws, sizes)`, "remove_bad_endings": 0 / 1}: the ranked rows and scores
+    are scored on the device in the same pass (subgc_diversity_select / _distinct / _best) -> d_int (int32 [sets, DIV_COLS + n_best]) and
+    d_f64 (fp64 [sets, n_best + 1]) in the same copy; `scorer.unpack(plan, d_int, d_f64)` makes the per-image entries.
+    accuracy: optional {"scorer": AccuracyScorer, "index": per-image reference-image indices, "remove_bad_endings": 0 / 1}: the ranked rows
+    are scored against their references on the device in the same pass (subgc_consensus_cook, subgc_accuracy_rows / _oracle of
+    subgc_metrics_hip.h); the top-1 row is the re-ranker's first choice, read from device memory, when `consensus` is given, row 0
+    otherwise -> a_words (int32: the scorer's result arena) in the same copy; `scorer.unpack(a_words, bounds)` makes the per-image entries.
+    With accuracy=None the arena, the launches and the outputs are what they are without it.
+    grounding: optional {"scorer": GroundingScorer, "index": per-image reference-image indices, "boxes": per image its fp32 boxes [N_i, 4]
+    in image scale (`grounding.prepare_boxes`), "remove_bad_endings": 0 / 1}; needs AL / idx.  Behind the grounding arg-max the chosen
+    captions become {'clss','idx_in_sent','bbox'} lists and precision / recall event codes on the device (subgc_grounding_material /
+    _score of subgc_grounding_hip.h); the boxes go up with the batch -> g_words (int32: the scorer's result arena) in the same copy and
+    g_plan; `scorer.unpack(g_words, g_plan)` makes the per-image entries.  With grounding=None nothing changes."""
+    P, stream, dev = ops._ptr, ops._stream(), score.device
+    rows, T = seq.shape
+    I = len(bounds) - 1
+    if bounds[-1] != rows or score.numel() != rows or keep.numel() != rows:
+        raise SubgcError("eval_collect: bounds / score / keep do not cover the rows of seq")
+    ground = AL is not None
+    T1 = AL.size(0) if ground else 0
+    # what the passes read: the batch's sizes now, `seg` / `seq_s` / `score_s` (the upload and the ranked rows) once they exist, and what
+    # earlier passes publish: `c_first`, then `pick` / `node` / `n_words` of the grounding arg-max
+    b = SimpleNamespace(I=I, rows=rows, T=T, T1=T1, bounds=bounds, ground=ground, max_rows=max([y - x for x, y in zip(bounds, bounds[1:])] + [0]),
+                        c_first=None)
+    slots = Slots(list(bounds))                                         # the bounds lead the upload: the kernels' `seg`
+    s_pick = slots.ints([0] * I if pick is None else [int(p) for p in pick])
+    w_order, w_score, w_keep, w_seq = slots.words(rows), slots.words(rows), slots.words(rows), slots.words(rows * T)
+    if ground:
+        w_att2, w_node, w_nw = slots.words(I * T1), slots.words(I * T1), slots.words(I)
+    # the passes, in launch order: each validates and reserves now, launches and reads back below
+    passes = [(name, *arg["reranker" if name == "consensus" else "scorer"].batch_pass(arg, b, slots))
+              for name, arg in (("consensus", consensus), ("diversity", diversity), ("accuracy", accuracy), ("grounding", grounding))
+              if arg is not None]
+    b.seg = slots.seg = ops.upload(slots.values, torch.int32, dev)
+    arena = slots.arena = torch.empty(max(slots.n_words, 1), device=dev, dtype=torch.int32)
+    order, keep_s = arena[w_order], arena[w_keep]
+    b.score_s, b.seq_s = arena[w_score].view(torch.float32), arena[w_seq].view(rows, T)
+    # the rows as both launches read them, held until the last is enqueued; a batch without rows has no storage, and the arg-max, which
+    # then reads none, refuses a null pointer
+    seq_c = seq.contiguous()
+    p_seq = P(seq_c, torch.int64) if rows else arena.data_ptr()
+    if I and rows:
+        call("subgc_eval_rank_rows", P(score.contiguous(), torch.float32), P(keep.contiguous(), torch.int64), p_seq,
+             T, P(b.seg), I, b.max_rows, int(bool(identity)), P(order), P(b.score_s), P(keep_s), P(b.seq_s), stream)
+    for name, enqueue, _ in passes:
+        if name != "grounding":
+            enqueue()
+    if ground:
+        att2, b.node, b.n_words = arena[w_att2], arena[w_node], arena[w_nw]
+        if AL.stride(2) != 1 or idx.stride(1) != 1:
+            raise SubgcError("eval_collect: AL / idx need unit inner strides")
+        if I:
+            # the caption the entry describes: an explicit pick, else the re-ranker's first choice, else 0
+            b.pick = b.seg[s_pick] if pick is not None else (b.c_first if (b.c_first is not None and rows) else None)
+            call("subgc_grounding_argmax", P(AL, torch.float32), AL.stride(0), AL.stride(1), AL.size(2), T1, p_seq, T,
+                 P(idx, torch.int64), idx.stride(0), P(b.seg), P(order) if (rows and not identity) else None, P(b.pick), I, P(att2),
+                 P(b.node), P(b.n_words), stream)
+    for name, enqueue, _ in passes:
+        if name == "grounding":
+            enqueue()
+    host = arena.cpu().numpy()                                          # the one copy (synchronises the stream)
+    out = {"order": host[w_order].astype(np.int64), "score": host[w_score].view(np.float32).copy(), "keep": host[w_keep].astype(np.int64),
+           "seq": host[w_seq].reshape(rows, T).astype(np.int64)}
+    if ground:
+        out.update(att2=host[w_att2].reshape(I, T1).copy(), node=host[w_node].reshape(I, T1).copy(), n_words=host[w_nw].copy())
+    for _, _, results in passes:
+        out.update(results(host))
+    return out
 
 
 @torch.no_grad()
@@ -145,50 +269,25 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                                grd_pick=None if grd_pick is None else [grd_pick[i] for i in idx], consensus=consensus, diversity=diversity, accuracy=accuracy,
                                grounding=grounding, controllability=controllability)
         return parallel.gather_by_index(local, idx, len(images))
+    from . import accuracy as accuracy_m, consensus as consensus_m, diversity as diversity_m, grounding as grounding_m
     sct_mode = eval_kwargs.get("sct", 0) == 1
     rbe = eval_kwargs.get("remove_bad_endings", 0)
     return_att = eval_kwargs.get("return_att", 0) == 1
     if grd_pick is not None and len(grd_pick) != len(images):
         raise ValueError("caption_images: one grd_pick entry per image")
-    if consensus is not None:
-        if sct_mode:
-            raise ValueError("caption_images: consensus re-ranking is not defined in sct (controllability) mode: its captions keep the "
-                             "input order and are not ranked")
-        missing = [info["id"] for info in infos if info["id"] not in consensus["nn"]]
+    given = {"consensus": consensus, "diversity": diversity, "accuracy": accuracy, "grounding": grounding, "controllability": controllability}
+    mods = {"consensus": consensus_m, "diversity": diversity_m, "accuracy": accuracy_m, "grounding": grounding_m}
+    live = [(name, d, given[name]) for name, d in _OPTIONS.items() if given[name] is not None]
+    for name, d, opt in live:
+        if sct_mode != d["only_sct"]:
+            raise ValueError(f"caption_images: {d['what']} {d['verbs'][0]} " + (_ONLY_SCT if d["only_sct"] else _NOT_IN_SCT))
+        if d["att"] and not return_att:
+            raise ValueError(f"caption_images: {d['what']} {d['verbs'][1]} eval_kwargs['return_att'] = 1 (the attention arg-max of every word)")
+        missing = [info["id"] for info in infos if any(info["id"] not in opt[k] for k in d["covers"])]
         if missing:
-            raise ValueError(f"caption_images: consensus['nn'] has no neighbour list for image ids {missing[:5]}")
-    if diversity is not None:
-        if sct_mode:
-            raise ValueError("caption_images: diversity scores are not defined in sct (controllability) mode: its captions keep the input "
-                             "order and are not ranked")
-        from .diversity import TOP_N, per_image_draws
-        d_scorer, d_top_n, d_seed = diversity["scorer"], tuple(diversity.get("top_n", TOP_N)), diversity.get("seed", 2019)
-    if accuracy is not None:
-        if sct_mode:
-            raise ValueError("caption_images: accuracy scores are not defined in sct (controllability) mode: its captions keep the input "
-                             "order and are not ranked")
-        missing = [info["id"] for info in infos if info["id"] not in accuracy["index"]]
-        if missing:
-            raise ValueError(f"caption_images: accuracy['index'] names no reference image for image ids {missing[:5]}")
-        a_scorer = accuracy["scorer"]
-    if grounding is not None:
-        if sct_mode:
-            raise ValueError("caption_images: grounding scores are not defined in sct (controllability) mode: its captions keep the input "
-                             "order and are not ranked")
-        if not return_att:
-            raise ValueError("caption_images: grounding scores need eval_kwargs['return_att'] = 1 (the attention arg-max of every word)")
-        missing = [info["id"] for info in infos if info["id"] not in grounding["index"] or info["id"] not in grounding["boxes"]]
-        if missing:
-            raise ValueError(f"caption_images: grounding['index'] / ['boxes'] name no reference image or no boxes for image ids {missing[:5]}")
-        from .grounding import prepare_boxes
-        g_scorer, g_wh = grounding["scorer"], grounding.get("img_wh")
+            raise ValueError(f"caption_images: {d['lacks']} for image ids {missing[:5]}")
+    batch_opts = [(name, d, opt, mods[name]) for name, d, opt in live if name in mods]      # those that ride in the decode batch's pass
     if controllability is not None:
-        if not sct_mode:
-            raise ValueError("caption_images: controllability scores are defined only in sct (controllability) mode (eval_kwargs['sct'] = 1): "
-                             "they need one caption per input region set, in input order")
-        missing = [info["id"] for info in infos if info["id"] not in controllability["index"]]
-        if missing:
-            raise ValueError(f"caption_images: controllability['index'] names no first group for image ids {missing[:5]}")
         c_scorer = controllability["scorer"]
         firsts = sorted(set(int(v) for v in controllability["index"].values())) + [c_scorer.refs.n_groups]
         c_count = {a: b - a for a, b in zip(firsts, firsts[1:])}
@@ -203,15 +302,10 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
             chunk, chunk_infos = images[i:i + group], infos[i:i + group]
             hold = {"skip_att": True}
             results = model.sample_images(chunk, opt=eval_kwargs) if sct_mode else _sample_batch(model, chunk, eval_kwargs, hold)
-            if "bounds" not in hold and consensus is not None:
-                raise ValueError("caption_images: consensus re-ranking needs a model whose sample_images exposes the decode batch (batch_out)")
-            if "bounds" not in hold and diversity is not None:
-                raise ValueError("caption_images: diversity scores need a model whose sample_images exposes the decode batch (batch_out)")
-            if "bounds" not in hold and accuracy is not None:
-                raise ValueError("caption_images: accuracy scores need a model whose sample_images exposes the decode batch (batch_out)")
-            if grounding is not None and ("bounds" not in hold or hold.get("AL") is None):
-                raise ValueError("caption_images: grounding scores need a model whose sample_images exposes the decode batch and its attention "
-                                 "buffer (batch_out)")
+            for _, d, _, _ in batch_opts:
+                if "bounds" not in hold or (d["att"] and hold.get("AL") is None):
+                    raise ValueError(f"caption_images: {d['what']} {d['verbs'][1]} a model whose sample_images exposes the decode batch"
+                                     f"{' and its attention buffer' if d['att'] else ''} (batch_out)")
             if "bounds" not in hold:
                 # per image: controllability mode (input order, first half, no ranking; rare) and models whose sample_images does not
                 # expose the batch tensors
@@ -225,62 +319,36 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                     _score_controllability(c_scorer, controllability["index"], c_count, chunk_infos, kept, predictions[len(predictions) - len(kept):], rbe)
                 continue
             bounds = hold["bounds"]
-            div = None
-            if diversity is not None:
-                sizes = [b - a for a, b in zip(bounds, bounds[1:])]
-                d_plan = d_scorer.plan(per_image_draws(sizes, [info["id"] for info in chunk_infos], d_top_n, d_seed), sizes)
-                div = {"scorer": d_scorer, "plan": d_plan, "remove_bad_endings": rbe}
+            ids, sizes = [info["id"] for info in chunk_infos], [b - a for a, b in zip(bounds, bounds[1:])]
+            args = {}
+            for name, d, opt, mod in batch_opts:                        # id-keyed dicts -> the chunk's lists; then what only the scorer knows
+                args[name] = dict(opt, remove_bad_endings=rbe, **{k: [opt[k][x] for x in ids] for k in d["covers"]})
+                if d.get("chunk_arg"):
+                    args[name] = mod.chunk_arg(args[name], opt, ids, sizes)
             if hold["rows"] == 0:
-                d_none = None if div is None else d_scorer.unpack(d_plan, np.zeros((d_plan["n_sets"], ops.DIV_COLS + d_scorer.n_best), np.int32),
-                                                                  np.zeros((d_plan["n_sets"], d_scorer.n_best + 1)), d_top_n)
-                for j, info in enumerate(chunk_infos):
-                    predictions.append({"image_id": info["id"], "caption": [], "subgraph_score": np.zeros(0, np.float32),
+                gained = [mod.chunk_entries(args[name], None, bounds) for name, _, _, mod in batch_opts]
+                for j, k in enumerate(ids):
+                    predictions.append({"image_id": k, "caption": [], "subgraph_score": np.zeros(0, np.float32),
                                         "sorted_subgraph_ind": np.zeros(0, np.int64)})
-                    if consensus is not None:
-                        predictions[-1].update(consensus_rerank_ind=np.zeros(0, np.int64), consensus_sim=np.zeros(0, np.float64))
-                    if div is not None:
-                        predictions[-1]["diversity"] = d_none[j]
-                    if accuracy is not None:
-                        predictions[-1]["accuracy"] = a_scorer.unpack(np.zeros(a_scorer.arena_words(0, 1), np.int32), [0, 0])[0]
-                    if grounding is not None:
-                        predictions[-1]["grounding_score"] = g_scorer.empty_entry(g_scorer.check_index([grounding["index"][info["id"]]])[0])
+                    for per_image in gained:
+                        predictions[-1].update(per_image[j])
                 continue
             ground = return_att and hold.get("AL") is not None
             pick = None if grd_pick is None else grd_pick[i:i + group]
             # eval_utils.py:105-115 for every image of the batch + grd_utils.py:36-47: two launches, one host copy
-            h = ops.eval_collect(hold["score"], hold["keep"], hold["seq"], bounds, identity=not model.gpn,
-                                 AL=hold["AL"] if ground else None, idx=hold["idx"] if ground else None, pick=pick if ground else None,
-                                 consensus=None if consensus is None else {
-                                     "reranker": consensus["reranker"], "nn": [consensus["nn"][info["id"]] for info in chunk_infos],
-                                     "top_k": consensus.get("top_k"), "remove_bad_endings": rbe}, diversity=div,
-                                 accuracy=None if accuracy is None else {
-                                     "scorer": a_scorer, "index": [accuracy["index"][info["id"]] for info in chunk_infos], "remove_bad_endings": rbe},
-                                 grounding=None if grounding is None else {
-                                     "scorer": g_scorer, "index": [grounding["index"][info["id"]] for info in chunk_infos], "remove_bad_endings": rbe,
-                                     "boxes": [prepare_boxes(grounding["boxes"][info["id"]], None if g_wh is None else g_wh[info["id"]])
-                                               for info in chunk_infos]})
-            g_entries = None if grounding is None else g_scorer.unpack(h["g_words"], h["g_plan"])
-            a_entries = None if accuracy is None else a_scorer.unpack(h["a_words"], bounds)
-            d_entries = None if div is None else d_scorer.unpack(d_plan, h["d_int"], h["d_f64"], d_top_n)
-            ctk = None if consensus is None else consensus.get("top_k")
-            for j, (info, a, b) in enumerate(zip(chunk_infos, bounds, bounds[1:])):
-                entry = {"image_id": info["id"], "caption": decode_sequence(ix_to_word, h["seq"][a:b], rbe),
+            h = eval_collect(hold["score"], hold["keep"], hold["seq"], bounds, identity=not model.gpn,
+                             AL=hold["AL"] if ground else None, idx=hold["idx"] if ground else None, pick=pick if ground else None, **args)
+            gained = [mod.chunk_entries(args[name], h, bounds) for name, _, _, mod in batch_opts]
+            for j, (k, a, b) in enumerate(zip(ids, bounds, bounds[1:])):
+                entry = {"image_id": k, "caption": decode_sequence(ix_to_word, h["seq"][a:b], rbe),
                          "subgraph_score": h["score"][a:b], "sorted_subgraph_ind": h["keep"][a:b]}
-                if consensus is not None:
-                    nc = (b - a) if not ctk else min(b - a, int(ctk))
-                    entry["consensus_rerank_ind"] = h["c_order"][a:a + nc].astype(np.int64)
-                    entry["consensus_sim"] = h["c_sim"][a:a + nc].copy()
-                if div is not None:
-                    entry["diversity"] = d_entries[j]
-                if accuracy is not None:
-                    entry["accuracy"] = a_entries[j]
                 if ground:
                     w = int(h["n_words"][j])
                     sub = int(pick[j]) if pick is not None else (int(h["c_first"][j]) if consensus is not None else 0)
                     entry["grounding"] = {"subg_index": sub, "sort_ind": h["order"][a:b],
                                           "att2_ind": h["att2"][j, :w].astype(np.int64), "node_ind": h["node"][j, :w].astype(np.int64)}
-                    if grounding is not None:
-                        entry["grounding_score"] = g_entries[j]
+                for per_image in gained:
+                    entry.update(per_image[j])
                 predictions.append(entry)
     finally:
         model.train(was_training)
@@ -378,7 +446,6 @@ def ground_gt_images(model, images, infos, gt, group=64):
     "caption_ll": {"ll" fp64, "n_tok" int32, "perplexity" fp64} per caption}; `grounding_gt.summarize` of the "gt_grounding" entries gives
     grd_accu, `grounding_gt.to_submission` the dict the reference evaluator reads.  Not sharded."""
     from . import forced
-    from ._lib import SubgcError, call
     from .grounding import prepare_boxes
     scorer, wh = gt["scorer"], gt.get("img_wh")
     if len(infos) != len(images):

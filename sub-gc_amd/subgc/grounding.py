@@ -21,7 +21,9 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _scoring
 from ._lib import SubgcError, call_grounding
+from ._scoring import csr as _csr
 
 # the codes and limits of subgc_grounding_hip.h
 MISS, HIT, SKIP, HALLUCINATED, ABSENT, NONE = 0, 1, 2, 3, 4, 255
@@ -39,10 +41,6 @@ def prepare_boxes(boxes, img_wh=None):
     if img_wh is not None:
         b = b * max(img_wh) / 592
     return np.ascontiguousarray(b, dtype=np.float32)
-
-
-def _csr(counts):
-    return np.concatenate([[0], np.cumsum(np.asarray(counts, np.int64))]).astype(np.int64)
 
 
 class GroundingReferences:
@@ -110,11 +108,8 @@ class GroundingReferences:
             if w in wd_to_lemma and wd_to_lemma[w] in lemma_det_id_dict:
                 self.tok_class[int(k)] = self.class_id[det[int(lemma_det_id_dict[wd_to_lemma[w]])]]
         self.device = None
-        if device == "auto":
-            import torch
-            device = torch.device("cuda", torch.cuda.current_device())
         if device is not None:
-            self.to(device)
+            self.to(_scoring.resolve_device(device))
 
     def _class(self, w):
         c = self.class_id.get(w)
@@ -147,11 +142,7 @@ class GroundingScorer:
         self.refs, self.iou_thresh = refs, float(iou_thresh)
 
     def check_index(self, image_index):
-        idx = [int(x) for x in image_index]
-        for i, j in enumerate(idx):
-            if not 0 <= j < self.refs.n_img:
-                raise SubgcError(f"grounding: batch image {i} names reference image {j}; the references hold {self.refs.n_img} images")
-        return idx
+        return _scoring.check_index("grounding", image_index, self.refs.n_img)
 
     def plan(self, image_index, counts=None):
         """The host side of a batch: which (image, caption) pairs it holds and where their events go.  counts: the predicted words of
@@ -180,11 +171,7 @@ class GroundingScorer:
     @staticmethod
     def views(arena, plan):
         """(mat_n [I], mat_cls [I, 64], mat_idx [I, 64], mat_box fp32 [I, 64, 4], prec uint8, rec uint8) views of an arena (torch or numpy)."""
-        if isinstance(arena, np.ndarray):
-            f32, u8 = np.float32, np.uint8
-        else:
-            import torch
-            f32, u8 = torch.float32, torch.uint8
+        f32, u8 = (ns := _scoring.dtypes(arena)).float32, ns.uint8
         I, W = plan["I"], MAX_WORDS
         o = I
         cls = arena[o:o + I * W].reshape(I, W); o += I * W
@@ -207,17 +194,14 @@ class GroundingScorer:
         from . import ops
         self._need_device()
         r = self.refs
-        if seq.dtype not in (torch.int32, torch.int64) or not seq.is_contiguous() or seq.dim() != 2:
-            raise SubgcError(f"grounding: contiguous int32 / int64 token rows [rows, T], got {seq.dtype} {tuple(seq.shape)}")
-        rows, T = seq.shape
-        if T > MAX_WORDS:
-            raise SubgcError(f"grounding: token rows of {T} words; the limit is {MAX_WORDS}")
+        t64, T = _scoring.token_rows("grounding", seq, MAX_WORDS)
+        rows = seq.size(0)
         if arena.numel() < self.arena_words(plan):
             raise SubgcError("grounding: the result arena is too short")
         mat_n, cls, idx, box, _, _ = self.views(arena, plan)
         bad = r.d_bad if remove_bad_endings else None
         P = ops._ptr
-        call_grounding("subgc_grounding_material", P(seq), int(seq.dtype == torch.int64), int(T), P(bad, torch.uint8), 0 if bad is None else bad.numel(),
+        call_grounding("subgc_grounding_material", P(seq), t64, int(T), P(bad, torch.uint8), 0 if bad is None else bad.numel(),
                        int(rows), P(seg, torch.int32), P(pick, torch.int32), int(I), P(node, torch.int32), int(T1), P(n_words, torch.int32),
                        P(r.d_tok_class, torch.int32), len(r.tok_class), P(box_off, torch.int32), P(boxes, torch.float32), int(n_boxes), P(mat_n),
                        P(cls), P(idx), P(box), MAX_WORDS, ops._stream())
@@ -246,6 +230,28 @@ class GroundingScorer:
         n_t = len(plan["table"])
         self.enqueue_material(seq, seg, pick, I, node, T1, n_words, tables[n_t:n_t + I + 1], boxes, n_boxes, remove_bad_endings, arena, plan)
         self.enqueue_score(tables, arena, plan)
+
+    def batch_pass(self, arg, batch, slots):
+        """The grounding pass of `eval_collect` (arg: its `grounding=`), behind the grounding arg-max: the plan's table and the box offsets
+        go up with the batch, the boxes in an upload of their own; reads `batch.pick` / `node` / `n_words`."""
+        import torch
+        from . import ops
+        if not batch.ground:
+            raise SubgcError("eval_collect: grounding scores need the decode loop's attention buffer (AL / idx)")
+        I, plan = batch.I, self.plan(arg["index"])
+        if plan["I"] != I or len(arg["boxes"]) != I:
+            raise SubgcError("eval_collect: grounding needs one reference-image index and one box array per image")
+        boxes = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 4) for b in arg["boxes"]]
+        lens = [len(b) for b in boxes]
+        n_box, s_tab, w = sum(lens), slots.ints(plan["table"].tolist() + _csr(lens).tolist()), slots.words(self.arena_words(plan))
+
+        def enqueue():
+            if I:
+                d_box = ops.upload(np.concatenate(boxes).ravel() if n_box else np.zeros(4, np.float32), torch.float32, slots.arena.device)
+                self.enqueue(batch.seq_s, batch.seg, batch.pick, I, batch.node, batch.T1, batch.n_words, slots.seg[s_tab], d_box, n_box,
+                             arg.get("remove_bad_endings", 0), slots.arena[w], plan)
+
+        return enqueue, lambda host: {"g_words": host[w].copy(), "g_plan": plan}
 
     def unpack(self, host, plan):
         """The host copy of an arena -> per image a dict of plain numpy data: "ref" (its image in the references), "clss" (class ids),
@@ -285,7 +291,7 @@ class GroundingScorer:
         import torch
         r = self.refs
         if r.device is None:
-            r.to(torch.device("cuda", torch.cuda.current_device()) if device == "auto" else torch.device(device))
+            r.to(_scoring.resolve_device(device))
         I = len(items)
         host = np.zeros(I + 6 * I * MAX_WORDS, np.int32)
         mat_n, cls, widx, box, _, _ = self.views(host, {"I": I, "n_prec": 0, "n_rec": 0})
@@ -322,6 +328,20 @@ class GroundingScorer:
             if len(results[k]) != 1:
                 raise SubgcError(f"grounding: image {k} has {len(results[k])} submission entries; the evaluator asserts exactly 1")
         return self.score_entries([(j, results[k][0]) for j, k in picked], device)
+
+
+def chunk_arg(arg, opt, ids, sizes):
+    """`caption_images(grounding=opt)`: the chunk's list-keyed argument with its boxes prepared."""
+    wh = opt.get("img_wh")
+    return dict(arg, boxes=[prepare_boxes(b, None if wh is None else wh[k]) for b, k in zip(arg["boxes"], ids)])
+
+
+def chunk_entries(arg, h, bounds):
+    """What every image's entry gains from `eval_collect`'s outputs `h` (None: a batch without rows, `empty_entry` of every image)."""
+    sc = arg["scorer"]
+    if h is None:
+        return [{"grounding_score": sc.empty_entry(j)} for j in sc.check_index(arg["index"])]
+    return [{"grounding_score": e} for e in sc.unpack(h["g_words"], h["g_plan"])]
 
 
 def summarize(entries, refs):

@@ -18,8 +18,9 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import _scoring
 from ._lib import SubgcError, call_forced
-from .grounding import _csr
+from ._scoring import csr as _csr
 
 # the codes and limits of subgc_forced_hip.h
 MISS, HIT, UNGROUNDED, NOROW, NONE = 0, 1, 2, 3, 255
@@ -122,11 +123,7 @@ class GtGroundingScorer:
         self.refs, self.iou_thresh = refs, float(iou_thresh)
 
     def check_index(self, image_index):
-        idx = [int(x) for x in image_index]
-        for i, j in enumerate(idx):
-            if not 0 <= j < self.refs.n_img:
-                raise SubgcError(f"gt grounding: batch image {i} names reference image {j}; the references hold {self.refs.n_img} images")
-        return idx
+        return _scoring.check_index("gt grounding", image_index, self.refs.n_img)
 
     def plan(self, image_index, rows_per_image, has_rows=None):
         """The host side of a batch.  image_index: the reference image of every batch image; rows_per_image: the forced rows it brings,
@@ -165,11 +162,7 @@ class GtGroundingScorer:
     @staticmethod
     def views(arena, plan):
         """(mat_n [rows], mat_idx [rows, 64], mat_box fp32 [rows, 64, 4], codes uint8 [n_out]) views of an arena (torch or numpy)."""
-        if isinstance(arena, np.ndarray):
-            f32, u8 = np.float32, np.uint8
-        else:
-            import torch
-            f32, u8 = torch.float32, torch.uint8
+        f32, u8 = (ns := _scoring.dtypes(arena)).float32, ns.uint8
         R, W = plan["rows"], MAX_WORDS
         o = R
         idx = arena[o:o + R * W].reshape(R, W); o += R * W
@@ -250,7 +243,7 @@ class GtGroundingScorer:
         import torch
         r = self.refs
         if r.device is None:
-            r.to(torch.device("cuda", torch.cuda.current_device()) if device == "auto" else torch.device(device))
+            r.to(_scoring.resolve_device(device))
         flat = []
         for j, lst in items:
             for e in (lst or []):

@@ -12,6 +12,7 @@ import math
 import torch
 
 from ._lib import SubgcError, call, call_beam_att, call_consensus, call_criterion, call_selfcritical, lib
+from . import _scoring
 
 RELU, ACCUM = 1, 2
 FLOPS = {"on": False, "gemm": 0.0, "gemm_bytes": 0.0, "gemm_calls": 0}
@@ -1659,132 +1660,9 @@ def rank_desc(score):
 
 def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pick=None, consensus=None, diversity=None, accuracy=None,
                  grounding=None):
-    """The eval loop's per-image work for a whole decode batch (misc/eval_utils.py:105-121; grounding: misc/grd_utils.py:36-47):
-    one ranking launch (subgc_eval_rank_rows), one grounding launch when `AL` (the decode loop's attention buffer [T1, rows, N]) and
-    `idx` (the kept sub-graphs' node lists [rows, N]) are given, and ONE device -> host copy of everything.
-    score [rows] fp32, keep [rows] int64, seq [rows, T] int64, bounds: python list of the I + 1 row boundaries of the images,
-    pick: optional per-image subg_index list (default 0 = the best-ranked caption).
-    consensus: optional {"reranker": ConsensusReranker, "nn": per-image neighbour index lists, "top_k": int or None, "remove_bad_endings": 0 / 1}:
-    the ranked token rows are re-ranked on the device in the same pass (subgc_consensus_cook / _score / _rank) and, unless `pick` is
-    given, the grounding launch takes each image's pick from the re-ranker's first choice ON THE DEVICE; its outputs ride in the same copy.
-    -> dict of host numpy arrays: order / score / keep (int64) / seq (int64) [rows...], and with grounding att2 / node [I, T1], n_words [I];
-    with consensus c_order (int32 [rows]: image i's order in its first n_i' = min(n_i, top_k) slots), c_sim (fp64 [rows]), c_first [I].
-    diversity: optional {"scorer": DiversityScorer, "plan": its `plan(draws, sizes)`, "remove_bad_endings": 0 / 1}: the ranked rows and scores
-    are scored on the device in the same pass (subgc_diversity_select / _distinct / _best) -> d_int (int32 [sets, DIV_COLS + n_best]) and
-    d_f64 (fp64 [sets, n_best + 1]) in the same copy; `scorer.unpack(plan, d_int, d_f64)` makes the per-image entries.
-    accuracy: optional {"scorer": AccuracyScorer, "index": per-image reference-image indices, "remove_bad_endings": 0 / 1}: the ranked rows
-    are scored against their references on the device in the same pass (subgc_consensus_cook, subgc_accuracy_rows / _oracle of
-    subgc_metrics_hip.h); the top-1 row is the re-ranker's first choice, read from device memory, when `consensus` is given, row 0
-    otherwise -> a_words (int32: the scorer's result arena) in the same copy; `scorer.unpack(a_words, bounds)` makes the per-image entries.
-    With accuracy=None the arena, the launches and the outputs are what they are without it.
-    grounding: optional {"scorer": GroundingScorer, "index": per-image reference-image indices, "boxes": per image its fp32 boxes [N_i, 4]
-    in image scale (`grounding.prepare_boxes`), "remove_bad_endings": 0 / 1}; needs AL / idx.  Behind the grounding arg-max the chosen
-    captions become {'clss','idx_in_sent','bbox'} lists and precision / recall event codes on the device (subgc_grounding_material /
-    _score of subgc_grounding_hip.h); the boxes go up with the batch -> g_words (int32: the scorer's result arena) in the same copy and
-    g_plan; `scorer.unpack(g_words, g_plan)` makes the per-image entries.  With grounding=None nothing changes."""
-    import numpy as np
-    dev = score.device
-    rows, T = seq.shape
-    I = len(bounds) - 1
-    if bounds[-1] != rows or score.numel() != rows or keep.numel() != rows:
-        raise SubgcError("eval_collect: bounds / score / keep do not cover the rows of seq")
-    ground = AL is not None
-    T1 = AL.size(0) if ground else 0
-    a_index = [] if accuracy is None else accuracy["scorer"].check_index(accuracy["index"])
-    if accuracy is not None and len(a_index) != I:
-        raise SubgcError("eval_collect: accuracy needs one reference-image index per image")
-    g_tab = []
-    if grounding is not None:
-        if not ground:
-            raise SubgcError("eval_collect: grounding scores need the decode loop's attention buffer (AL / idx)")
-        g_sc = grounding["scorer"]
-        g_plan = g_sc.plan(grounding["index"])
-        if g_plan["I"] != I or len(grounding["boxes"]) != I:
-            raise SubgcError("eval_collect: grounding needs one reference-image index and one box array per image")
-        g_box = [np.ascontiguousarray(b, dtype=np.float32).reshape(-1, 4) for b in grounding["boxes"]]
-        g_tab = g_plan["table"].tolist() + np.concatenate([[0], np.cumsum([len(b) for b in g_box])]).astype(np.int64).tolist()
-        g_nbox = sum(len(b) for b in g_box)
-    seg = upload(list(bounds) + ([0] * I if pick is None else [int(p) for p in pick]) + a_index + g_tab, torch.int32, dev)
-    words = 3 * rows + rows * T + (2 * I * T1 + I if ground else 0)
-    o_cons = (words + 1) & ~1                                         # the fp64 sums need an 8-byte aligned slot
-    if consensus is not None:
-        words = o_cons + 3 * rows + I
-    if diversity is not None:
-        d_sets, d_nb = diversity["plan"]["n_sets"], diversity["scorer"].n_best
-        o_div = (words + 1) & ~1                                      # fp64 first: 8-byte aligned
-        words = o_div + d_sets * (2 * (d_nb + 1) + DIV_COLS + d_nb)
-    if accuracy is not None:
-        o_acc = (words + 1) & ~1                                      # fp64 first: 8-byte aligned
-        a_words = accuracy["scorer"].arena_words(rows, I)
-        words = o_acc + a_words
-    if grounding is not None:
-        o_grd = words
-        g_words = g_sc.arena_words(g_plan)
-        words = o_grd + g_words
-    arena = torch.empty(max(words, 1), device=dev, dtype=torch.int32)
-    o = 0
-    order = arena[o:o + rows]; o += rows
-    score_s = arena[o:o + rows].view(torch.float32); o += rows
-    keep_s = arena[o:o + rows]; o += rows
-    seq_s = arena[o:o + rows * T]; o += rows * T
-    max_rows = max([b - a for a, b in zip(bounds, bounds[1:])] + [0])
-    if I and rows:
-        call("subgc_eval_rank_rows", _ptr(score.contiguous(), torch.float32), _ptr(keep.contiguous(), torch.int64), _ptr(seq.contiguous(), torch.int64),
-             T, _ptr(seg), I, max_rows, int(bool(identity)), _ptr(order), _ptr(score_s), _ptr(keep_s), _ptr(seq_s), _stream())
-    c_first = None
-    if consensus is not None:
-        c_sim = arena[o_cons:o_cons + 2 * rows].view(torch.float64)
-        c_order = arena[o_cons + 2 * rows:o_cons + 3 * rows]
-        c_first = arena[o_cons + 3 * rows:o_cons + 3 * rows + I]
-        if I and rows:
-            consensus["reranker"].enqueue(seq_s.view(rows, T), seg, I, max_rows, consensus["nn"], consensus.get("top_k"),
-                                          consensus.get("remove_bad_endings", 0), c_sim, c_order, c_first)
-    if diversity is not None:
-        n_f64 = 2 * d_sets * (d_nb + 1)
-        if d_sets:
-            diversity["scorer"].enqueue(seq_s.view(rows, T), score_s, seg, I, diversity["plan"], diversity.get("remove_bad_endings", 0),
-                                        arena[o_div + n_f64:o_div + n_f64 + d_sets * (DIV_COLS + d_nb)].view(d_sets, DIV_COLS + d_nb),
-                                        arena[o_div:o_div + n_f64].view(torch.float64).view(d_sets, d_nb + 1))
-    if accuracy is not None and I and rows:
-        accuracy["scorer"].enqueue(seq_s.view(rows, T), seg, I, seg[2 * I + 1:3 * I + 1], c_first, accuracy.get("remove_bad_endings", 0),
-                                   arena[o_acc:o_acc + a_words])
-    if ground:
-        att2 = arena[o:o + I * T1]; o += I * T1
-        node = arena[o:o + I * T1]; o += I * T1
-        nw = arena[o:o + I]; o += I
-        if AL.stride(2) != 1 or idx.stride(1) != 1:
-            raise SubgcError("eval_collect: AL / idx need unit inner strides")
-        if I:
-            g_pick = seg[I + 1:2 * I + 1] if pick is not None else (c_first if (c_first is not None and rows) else None)
-            call("subgc_grounding_argmax", _ptr(AL, torch.float32), AL.stride(0), AL.stride(1), AL.size(2), T1, _ptr(seq.contiguous(), torch.int64), T,
-                 _ptr(idx, torch.int64), idx.stride(0), _ptr(seg), _ptr(order) if (rows and not identity) else None, _ptr(g_pick), I, _ptr(att2),
-                 _ptr(node), _ptr(nw), _stream())
-            if grounding is not None:
-                g_dbox = upload(np.concatenate(g_box).ravel() if g_nbox else np.zeros(4, np.float32), torch.float32, dev)
-                g_sc.enqueue(seq_s.view(rows, T), seg, g_pick, I, node, T1, nw, seg[2 * I + 1 + len(a_index):], g_dbox, g_nbox,
-                             grounding.get("remove_bad_endings", 0), arena[o_grd:o_grd + g_words], g_plan)
-    host = arena.cpu().numpy()                                        # the one copy (synchronises the stream)
-    o = 0
-    out = {"order": host[o:o + rows].astype(np.int64)}; o += rows
-    out["score"] = host[o:o + rows].view(np.float32).copy(); o += rows
-    out["keep"] = host[o:o + rows].astype(np.int64); o += rows
-    out["seq"] = host[o:o + rows * T].reshape(rows, T).astype(np.int64); o += rows * T
-    if ground:
-        out["att2"] = host[o:o + I * T1].reshape(I, T1).copy(); o += I * T1
-        out["node"] = host[o:o + I * T1].reshape(I, T1).copy(); o += I * T1
-        out["n_words"] = host[o:o + I].copy()
-    if consensus is not None:
-        out["c_sim"] = host[o_cons:o_cons + 2 * rows].view(np.float64).copy()
-        out["c_order"] = host[o_cons + 2 * rows:o_cons + 3 * rows].copy()
-        out["c_first"] = host[o_cons + 3 * rows:o_cons + 3 * rows + I].copy()
-    if diversity is not None:
-        out["d_f64"] = host[o_div:o_div + n_f64].view(np.float64).reshape(d_sets, d_nb + 1).copy()
-        out["d_int"] = host[o_div + n_f64:o_div + n_f64 + d_sets * (DIV_COLS + d_nb)].reshape(d_sets, DIV_COLS + d_nb).copy()
-    if accuracy is not None:
-        out["a_words"] = host[o_acc:o_acc + a_words].copy() if (I and rows) else np.zeros(a_words, np.int32)
-    if grounding is not None:
-        out["g_words"], out["g_plan"] = host[o_grd:o_grd + g_words].copy(), g_plan
-    return out
+    """The eval loop's per-image work for a whole decode batch: see `eval_glue.eval_collect`, which this forwards to."""
+    from .eval_glue import eval_collect as run
+    return run(score, keep, seq, bounds, identity, AL, idx, pick, consensus, diversity, accuracy, grounding)
 
 
 def consensus_cook(tok, ukeys, ulogdf, ref_len, woff=None, max_words=0, row_len=None, bad=None):
@@ -1873,9 +1751,8 @@ DIV_WANT = {1: 1, 2: 2, 3: 2, 4: 4}       # metric of diversity_score.py -> SUBG
 
 
 def _div_tok(who, tok):
-    if tok.dtype not in (torch.int32, torch.int64) or not tok.is_contiguous() or tok.dim() != 2:
-        raise SubgcError(f"{who}: contiguous int32 / int64 token rows [rows, T], got {tok.dtype} {tuple(tok.shape)}")
-    return _ptr(tok), int(tok.dtype == torch.int64), tok.size(1)
+    t64, T = _scoring.token_rows(who, tok)
+    return _ptr(tok), t64, T
 
 
 def diversity_select(score, seg, I, rows, set_img, set_off, draw, n_sets, n_draw, max_draw, n_best, out_i):

@@ -73,7 +73,8 @@ def test_every_attribute_read_on_a_package_module_exists():
 
 def test_every_entry_point_called_by_name_is_declared():
     protos = _lib.parse_header()
-    seen, missing = 0, []
+    keyed = {"call_" + key: (hdr, _lib.parse_header(os.path.join(os.path.dirname(_lib.HEADER), hdr))) for key, hdr in _lib.HEADERS.items() if key != "core"}
+    seen, missing, seen_keyed = 0, [], set()
     for path, _ in _sources():
         for node in ast.walk(ast.parse(open(path).read(), path)):
             if not isinstance(node, ast.Call) or not node.args:
@@ -85,13 +86,19 @@ def test_every_entry_point_called_by_name_is_declared():
                 seen += 1
                 if a0.value not in protos:
                     missing.append(f"{os.path.relpath(path, PKG)}:{node.lineno}: {a0.value}")
+            # call_metrics("subgc_xxx", ...) ... call_beam_att("subgc_xxx", ...): the name must be declared in THAT invoker's header
+            if name in keyed and isinstance(a0, ast.Constant) and isinstance(a0.value, str):
+                seen_keyed.add((name, a0.value))
+                if a0.value not in keyed[name][1]:
+                    missing.append(f"{os.path.relpath(path, PKG)}:{node.lineno}: {a0.value} (not in {keyed[name][0]})")
             # lib().subgc_xxx(...) / _lib.lib().subgc_xxx(...): direct calls through the CDLL
             if isinstance(f, ast.Attribute) and f.attr.startswith("subgc_") and isinstance(f.value, ast.Call):
                 seen += 1
                 if f.attr not in protos:
                     missing.append(f"{os.path.relpath(path, PKG)}:{node.lineno}: {f.attr}")
     assert seen > 100
-    assert not missing, "entry points called but not declared in subgc_hip.h:\n" + "\n".join(missing)
+    assert {n for n, _ in seen_keyed} == set(keyed) and len(seen_keyed) == 27      # every invoker is in use; every other header's entry point is called by name
+    assert not missing, "entry points called but not declared in their invoker's header:\n" + "\n".join(missing)
 
 
 def test_profiling_families_match_the_header():

@@ -39,12 +39,6 @@ def test_controllability_header_parses_and_the_other_three_are_untouched():
         "tok", "tok64", "T", "bad", "bad_n", "rows", "tok_noun", "n_tok_noun", "vec", "norm", "n_noun", "d", "row_group", "n_groups", "pair_off",
         "n_pairs", "gcap_off", "n_caps", "gn_off", "gn", "n_gn", "iou", "pair_iou", "pair_mn", "assign", "stream"]
     assert len(args) == N_ARGS and args[2][0] is ctypes.c_int and args[9][0] is ctypes.c_void_p
-    core, metrics, grounding = _lib.parse_header(), _lib.parse_header(_lib.METRICS_HEADER), _lib.parse_header(_lib.GROUNDING_HEADER)
-    assert len(core) == 133 and sorted(metrics) == ["subgc_accuracy_oracle", "subgc_accuracy_rows"]
-    assert sorted(grounding) == ["subgc_grounding_material", "subgc_grounding_score"]
-    assert not set(protos) & (set(core) | set(metrics) | set(grounding))
-    L = _lib.lib()
-    assert hasattr(L, "subgc_control_noun_iou") and L.subgc_version() == 1
     src = open(_lib.CONTROLLABILITY_HEADER).read()
     assert f"#define SUBGC_CTL_MAX_WORDS {C.MAX_WORDS} " in src and C.MAX_WORDS == 64
     assert "1e-8" in src and C.COS_EPS == 1e-8
@@ -72,15 +66,6 @@ def test_each_invoker_knows_only_its_own_header_and_arguments_are_validated_on_t
         _lib.call_controllability("subgc_control_noun_iou", *_args(n_gn=3))
     with pytest.raises(SubgcError, match="null pointer"):
         _lib.call_controllability("subgc_control_noun_iou", *_args(rows=2))
-    for name in ("subgc_debug_bounds", "subgc_accuracy_oracle", "subgc_grounding_score"):
-        with pytest.raises(SubgcError, match="not declared in subgc_controllability_hip.h"):
-            _lib.call_controllability(name, 0)
-    with pytest.raises(SubgcError, match="not declared in subgc_hip.h"):
-        _lib.call("subgc_control_noun_iou")
-    with pytest.raises(SubgcError, match="not declared in subgc_metrics_hip.h"):
-        _lib.call_metrics("subgc_control_noun_iou")
-    with pytest.raises(SubgcError, match="not declared in subgc_grounding_hip.h"):
-        _lib.call_grounding("subgc_control_noun_iou")
 
 
 @pytest.mark.parametrize("tag", G.SETS)
