@@ -24,6 +24,8 @@ HEADERS = {"core": "subgc_hip.h", "metrics": "subgc_metrics_hip.h", "grounding":
            "controllability": "subgc_controllability_hip.h", "criterion": "subgc_criterion_hip.h", "selfcritical": "subgc_selfcritical_hip.h",
            "consensus": "subgc_consensus_hip.h", "forced": "subgc_forced_hip.h", "control_input": "subgc_control_input_hip.h",
            "beam_att": "subgc_beam_att_hip.h"}
+# Headers outside the table above (its keys and entry-point counts are pinned by the header tests): parsed, bound and invoked the same way.
+EXTRA_HEADERS = {"decode_b16": "subgc_decode_b16_hip.h"}
 HEADER = os.path.join(_INCLUDE, HEADERS["core"])
 METRICS_HEADER = os.path.join(_INCLUDE, HEADERS["metrics"])
 GROUNDING_HEADER = os.path.join(_INCLUDE, HEADERS["grounding"])
@@ -34,6 +36,7 @@ CONSENSUS_HEADER = os.path.join(_INCLUDE, HEADERS["consensus"])
 FORCED_HEADER = os.path.join(_INCLUDE, HEADERS["forced"])
 CONTROL_INPUT_HEADER = os.path.join(_INCLUDE, HEADERS["control_input"])
 BEAM_ATT_HEADER = os.path.join(_INCLUDE, HEADERS["beam_att"])
+DECODE_B16_HEADER = os.path.join(_INCLUDE, EXTRA_HEADERS["decode_b16"])
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -90,7 +93,7 @@ def parse_struct(name, path=HEADER):
 
 
 _lib = None
-PROTOS = {}         # key of HEADERS -> its parsed prototypes; filled once by lib()
+PROTOS = {}         # key of HEADERS / EXTRA_HEADERS -> its parsed prototypes; filled once by lib()
 _protos = None      # PROTOS["core"]: what `call` checks
 
 
@@ -101,7 +104,7 @@ def lib():
             raise SubgcError(f"{LIB_PATH} is missing: run `python sub-gc_amd/build.py` (hipcc, gfx950). "
                              "There is no CPU fallback for the Sub-GC hot path.")
         L = ctypes.CDLL(LIB_PATH)
-        for key, hdr in HEADERS.items():
+        for key, hdr in {**HEADERS, **EXTRA_HEADERS}.items():
             PROTOS[key] = parse_header(os.path.join(_INCLUDE, hdr))
             for name, (ret, args) in PROTOS[key].items():
                 try:
@@ -134,8 +137,9 @@ def call(name, *args):
 
 
 def _invoker(key):
-    """`call` for the entry points of one header of HEADERS: a cache of its own, so that no invoker reaches another's declarations."""
-    cache, hdr = {}, HEADERS[key]
+    """`call` for the entry points of one header of HEADERS / EXTRA_HEADERS: a cache of its own, so that no invoker reaches another's
+    declarations."""
+    cache, hdr = {}, HEADERS[key] if key in HEADERS else EXTRA_HEADERS[key]
 
     def invoke(name, *args):
         fn = cache.get(name)
@@ -160,6 +164,7 @@ call_consensus = _invoker("consensus")
 call_forced = _invoker("forced")
 call_control_input = _invoker("control_input")
 call_beam_att = _invoker("beam_att")
+call_decode_b16 = _invoker("decode_b16")
 
 FAM = {"gemm": 1, "attn": 2, "lstm": 3, "gcn": 4, "pool": 5, "softmax": 6}
 

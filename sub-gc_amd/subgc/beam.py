@@ -90,14 +90,15 @@ def _beam_step(grp, vals, idx, tau, bd, unk, constraint, earlier, lam):
 class _BatchEngine:
     """All sub-graphs x beams of an image batch as rows of one DecodeState (the product path)."""
 
-    def __init__(self, pr, P, N, beam, xt_table=None, snapshots=None, return_att=False):
+    def __init__(self, pr, P, N, beam, xt_table=None, snapshots=None, return_att=False, W16=None, b16_batched=False):
         n, dev = pr.S, pr.f.device
         self.n, self.rows, self.dev = n, n * beam, dev
         rep = torch.arange(n, device=dev).repeat_interleave(beam)
         prb = SimpleNamespace(S=self.rows, N=N, f=pr.f.index_select(0, rep).contiguous(), u=pr.u, v=pr.v,
                               off=pr.off.index_select(0, rep).contiguous(), lens=pr.lens.index_select(0, rep).contiguous())
         self.pr, self.prb, self.rep = pr, prb, rep
-        self.st = F_.DecodeState(prb, P, N, bool(return_att), xt_table=xt_table, fuse_lstm=True, snapshots=snapshots)    # fused for <= 32 rows
+        self.st = F_.DecodeState(prb, P, N, bool(return_att), xt_table=xt_table, fuse_lstm=True, snapshots=snapshots,      # fused for <= 32 rows
+                                   W16=W16, b16_batched=b16_batched)                  # default: no twins, beam search streams the fp32 weights
         self.V1 = self.st.V1
         self.alpha = torch.empty(self.rows, N, device=dev, dtype=torch.float32) if return_att else None    # host `search`: the last step's rows
 
@@ -126,10 +127,13 @@ class _BatchEngine:
         return self.alpha.cpu().numpy()
 
     def reorder(self, src):
+        if self.st.b16 and src.size and not (0 <= int(src.min()) and int(src.max()) < self.rows):      # the host knows these rows: refuse, not clamp
+            from ._lib import SubgcError
+            raise SubgcError(f"beam fork: source rows {int(src.min())} .. {int(src.max())} outside the state's {self.rows} rows")
         self.st.reorder(torch.from_numpy(src).to(self.dev))
 
     def snapshot(self):
-        return [x.clone() for x in self.st.recurrent()]
+        return [x.clone() for x in self.st.recurrent()]       # bf16 [h2 | h1] and h2 slot, fp32 c1, c2 in the bf16-batched regime
 
     def restore(self, rows, snap):
         sel = torch.from_numpy(rows.astype(np.int64)).to(self.dev)
@@ -176,7 +180,7 @@ class _StepEngine:
 
 
 @torch.no_grad()
-def beam_decode(pr, P, N, T, opt, xt_table=None, on_device=True, return_att=False):
+def beam_decode(pr, P, N, T, opt, xt_table=None, on_device=True, return_att=False, W16=None, b16_batched=False):
     """Decode every sub-graph of `pr` (an F_.Prepared) with beam search.
     Returns (seq [n, T] int64, seqLogprobs [n, T] fp32, done_beams) -- CPU tensors, as the reference's are.
     `on_device` (default): the candidate bookkeeping runs in `subgc_beam_step`, the loop has no host round trip;
@@ -185,7 +189,7 @@ def beam_decode(pr, P, N, T, opt, xt_table=None, on_device=True, return_att=Fals
     attention rows of every sub-graph's winning beam, AL[w, s] = the distribution of the decoder step whose logits produced word w of
     seq[s], zero for w >= len[s] (len counts the end token and is T for a beam cut at the last step).  Beam search never feeds its last
     word (CaptionModel.py:170-171), so unlike a greedy decode there is no attention row behind the last word: AL[T] is all zero."""
-    eng = _BatchEngine(pr, P, N, int(opt.get("beam_size", 10)), xt_table, return_att=return_att)
+    eng = _BatchEngine(pr, P, N, int(opt.get("beam_size", 10)), xt_table, return_att=return_att, W16=W16, b16_batched=b16_batched)
     return search_device(eng, T, opt, return_att) if on_device else search(eng, T, opt, return_att)
 
 

@@ -134,7 +134,7 @@ def forced_decode(model, images, tokens, return_att=False, batch_out=None):
             P = model._decoder_params()
             pr = F_.Prepared(fc, X2, lens, idx, img, N, P, None, None, 1.0)
             st = F_.DecodeState(pr, P, N, return_att, xt_table=model.xt_gates_table(), fuse_lstm=True, snapshots=model.decode_snapshots(),
-                                W16=model.decode_w16())
+                                W16=model.decode_w16(), b16_batched=model.decode_b16_on())
             if st.V1 > MAX_V:
                 raise SubgcError(f"forced_decode: {st.V1} logit columns; the limit is {MAX_V}")
             z = lambda *s, dt=torch.float32: ops.zero_(torch.empty(*s, device=dev, dtype=dt))

@@ -914,6 +914,13 @@ def _cat_weights(w_ih_part, w_hh):
     return out
 
 
+def _b16_rows(S, cols, dev):
+    """A zeroed bf16 [S, cols] product operand at the decoder's row pitch (ops.PITCH) and the fp32 word view of its whole buffer, pad
+    columns included (bf16 zero is the all-zero bit pattern: `ops.fill_` on the words restarts it)."""
+    words = ops.zeros(S, ops.pitch_of(cols, True) // 2, device=dev)
+    return words.view(ops.BF16)[:, :cols], words
+
+
 _STEP_OFFSETS = {}
 
 
@@ -1290,7 +1297,7 @@ def prepared_backward(pr, P, W, bf, fc_in, X_nodes, du, dv, df, scale, out_for, 
 class DecodeState:
     """Step-wise decoder for sampling (AttModel._sample loop body): same kernels, batch n."""
 
-    def __init__(self, pr: Prepared, P, N, want_att, xt_table=None, fuse_lstm=False, snapshots=None, W16=None):
+    def __init__(self, pr: Prepared, P, N, want_att, xt_table=None, fuse_lstm=False, snapshots=None, W16=None, b16_batched=False):
         """`xt_table` [V+1, 4R] (optional, frozen weights only): relu(Emb) . W_ih[:, 2R:]^T, one row per token -- the x->gates
         product of the attention LSTM looked up instead of recomputed every step (AttModel.xt_gates_table).
         `fuse_lstm` (<= 32 rows, R % 4 == 0): each LSTM cell is ONE launch, gate GEMM + cell update (subgc_lstm_step_skinny) on
@@ -1304,7 +1311,8 @@ class DecodeState:
         # `W16` (compute_dtype = bf16; list aligned with P, see bf16_twins): the fused (<= 32 row) step streams bf16-STORED weights --
         # both LSTM matrices, h2att (<= 16 rows) and the logit layer -- against fp32 activations with fp32 accumulation: half the
         # bytes of the weight stream that bounds the one-image decode; cell state, attention and the pick stay fp32
-        self.w16 = W16 if (self.fused and W16 is not None and all(W16[i] is not None for i in (9, 10, 13, 14, 17, 21))) else None
+        twins = W16 is not None and all(W16[i] is not None for i in (9, 10, 13, 14, 17, 21))
+        self.w16 = W16 if (self.fused and twins) else None
         (_, _, _, _, _, _, _, _, self.emb, w1i, w1h, self.b1i, self.b1h, w2i, w2h, self.b2i, self.b2h,
          self.h2a_w, self.h2a_b, self.an_w, self.an_b, self.lg_w, self.lg_b) = P
         self.pr, self.N = pr, N
@@ -1312,6 +1320,19 @@ class DecodeState:
         S = pr.S
         R, E = w1h.size(1), self.emb.size(1)
         self.S, self.R, self.E, self.A, self.V1 = S, R, E, self.h2a_w.size(0), self.lg_w.size(0)
+        # `b16_batched` (opt.decode_b16_batched, > 32 rows, every twin present): the third bf16 regime.  The step's five products run on
+        # bf16 operands (subgc_gemm_bf16, fp32 accumulation and output): h and ctx are STORED bf16 inside [h_lang | h_att] and
+        # [ctx | h_att | h_lang], rounded once by their producers (subgc_decode_cell_b16, subgc_attn_fwd), the weights are the twins
+        # (K-concatenated in natural gate order under the snapshot key "cat16"); c1, c2, the pre-activations, the attention sets and
+        # the logits stay fp32, so the pick kernels are untouched.  A missing twin leaves the fp32 regime, as for the fused ones.
+        self.b16 = bool(b16_batched) and S > 32 and twins
+        if self.b16:
+            if R % 8 or E % 8 or self.A % 8:
+                raise ops.SubgcError(f"bf16-batched decode needs rnn_size, input_encoding_size and att_hid_size to be multiples of 8, got R = {R}, "
+                                     f"E = {E}, A = {self.A}")
+            self.W1x = w1i[:, 2 * R:]                            # fp32: read by the table-less step only
+            self._init_b16(W16, snapshots, want_att, dev)
+            return
         key = ("perm16" if self.w16 is not None else "perm") if self.fused else "cat"
         if snapshots is not None and key in snapshots:
             self.Wc1, self.Wc2 = snapshots[key]
@@ -1344,6 +1365,46 @@ class DecodeState:
         self._alt = None
         self.lg_op = self.w16[21] if (self.w16 is not None and S <= 16) else self.lg_w        # the logit matrix as the skinny launches stream it
 
+    def _init_b16(self, W16, snapshots, want_att, dev):
+        """Buffers and snapshots of the bf16-batched regime (see __init__)."""
+        S, R = self.S, self.R
+        self.w16 = W16
+        if snapshots is not None and "cat16" in snapshots:
+            self.Wc1, self.Wc2 = snapshots["cat16"]
+        else:
+            self.Wc1 = _cat_weights(W16[9][:, :R], W16[10])
+            self.Wc2 = _cat_weights(W16[13], W16[14])
+            if snapshots is not None:
+                snapshots["cat16"] = (self.Wc1, self.Wc2)
+        new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)
+        self.W1f = W16[9][:, R:2 * R]
+        self.f16 = ops.empty_b16(S, self.pr.f.size(1), dev)
+        self.Gf = new(S, 4 * R)
+        (self.H1, self._H1w), (self.H2, self._H2w) = _b16_rows(S, 2 * R, dev), _b16_rows(S, 3 * R, dev)      # [h2 | h1], [ctx | h1 | h2]
+        self.hout, _ = _b16_rows(S, R, dev)
+        self.C1 = [ops.zeros(S, R, device=dev), new(S, R)]
+        self.C2 = [ops.zeros(S, R, device=dev), new(S, R)]
+        self.xt, self.Gx, self.pre, self.ah = new(S, self.E), new(S, 4 * R), new(S, 4 * R), new(S, self.A)
+        self.logits = new(S, self.V1)
+        self.want_att = want_att
+        self._alt = None
+        self.lg_op = W16[21]
+        self._gf_b16()
+
+    def _gf_b16(self):
+        """Gf = fc . W1f^T once per decode on the twins: fc is rounded to bf16 here."""
+        ops.cast_bf16(self.pr.f, out=self.f16)
+        ops.gemm(self.f16, self.W1f, self.Gf, tb=True)
+
+    @property
+    def regime(self):
+        """What the step streams: "fp32" | "bf16" (<= 16 rows) | "lstm-bf16" (17 .. 32) | "bf16-batched" (> 32, opt-in)."""
+        if self.b16:
+            return "bf16-batched"
+        if self.w16 is None:
+            return "fp32"
+        return "bf16" if self.S <= 16 else "lstm-bf16"
+
     def _h2att(self):
         """ah = h2att(h1): the weight-streaming form on the bf16 twin when there is one (<= 16 rows), else the fp32 product."""
         R = self.R
@@ -1360,6 +1421,11 @@ class DecodeState:
 
     def reset(self):
         """Start a new decode on the SAME buffers (hipGraph replay: `pr`'s tensors were overwritten in place)."""
+        if self.b16:
+            self._gf_b16()
+            for buf in (self._H1w, self._H2w, self.C1[0], self.C2[0]):      # bf16 zero is the all-zero bit pattern: the word views
+                ops.fill_(buf, 0.0)
+            return
         ops.gemm(self.pr.f, self.W1f, self.Gf, tb=True)
         for buf in (self.H1, self.H2, self.C1[0], self.C2[0]):
             ops.fill_(buf, 0.0)
@@ -1372,6 +1438,8 @@ class DecodeState:
 
     def reorder(self, src):
         """state[row] <- state[src[row]] for every row (src: int32 [S] on the device)."""
+        if self.b16:
+            return self._reorder_b16(src)
         if self._alt is None:
             self._alt = [torch.empty_like(self.H1), torch.empty_like(self.H2), torch.empty_like(self.C1[0]), torch.empty_like(self.C2[0])]
         a1, a2, ac1, ac2 = self._alt
@@ -1379,6 +1447,43 @@ class DecodeState:
         ops.gather_rows_multi([(self.H1, a1), (self.H2[:, 2 * R:], a2[:, 2 * R:]), (self.C1[0], ac1), (self.C2[0], ac2)], src)
         self._alt = [self.H1, self.H2, self.C1[0], self.C2[0]]
         self.H1, self.H2, self.C1[0], self.C2[0] = a1, a2, ac1, ac2
+
+    def _reorder_b16(self, src):
+        """`reorder` for the bf16-batched state: the two bf16 and the two fp32 tensors in one launch (subgc_decode_fork_b16), into the
+        alternate buffer set, which then becomes the current one."""
+        S, R = self.S, self.R
+        dev = self.C1[0].device
+        if src.numel() != S:
+            raise ops.SubgcError(f"reorder: {src.numel()} source rows for a state of {S}")
+        if self._alt is None:
+            self._alt = [_b16_rows(S, 2 * R, dev), _b16_rows(S, 3 * R, dev), torch.empty_like(self.C1[0]), torch.empty_like(self.C2[0])]
+        (a1, a1w), (a2, a2w), ac1, ac2 = self._alt
+        ops.decode_fork_b16([(self.H1, a1), (self.H2[:, 2 * R:], a2[:, 2 * R:])], [(self.C1[0], ac1), (self.C2[0], ac2)], src)
+        self._alt = [(self.H1, self._H1w), (self.H2, self._H2w), self.C1[0], self.C2[0]]
+        self.H1, self._H1w, self.H2, self._H2w, self.C1[0], self.C2[0] = a1, a1w, a2, a2w, ac1, ac2
+
+    def _step_b16(self, it, alpha_out, normalize):
+        """One step of the bf16-batched regime: five bf16 products with fp32 results around two cells and the attention."""
+        S, R, A = self.S, self.R, self.A
+        pr, W = self.pr, self.w16
+        if self.xt_table is not None:
+            table, tok, add = self.xt_table, it, None                      # the x->gates row is gathered inside the cell
+        else:
+            ops.embed_fwd(self.emb, it, 1, None, 1.0, self.xt)
+            ops.gemm(self.xt, self.W1x, self.Gx, tb=True)
+            table, tok, add = None, None, self.Gx
+        ops.gemm(self.H1, self.Wc1, self.pre, tb=True, add=add)
+        ops.decode_cell_b16(self.pre, self.C1[0], self.C1[1], [self.H2[:, R:2 * R], self.H1[:, R:]], self.b1i, self.b1h, table, tok, self.Gf)
+        self.C1.reverse()
+        ops.gemm(self.H2[:, R:2 * R], W[17], self.ah, tb=True, bias=self.h2a_b)
+        ops.attn_fwd(pr.u, pr.v, self.ah, self.an_w, self.an_b, pr.off, pr.lens, self.H2[:, :R], alpha_out, S, A, R)      # ctx lands bf16
+        ops.gemm(self.H2, self.Wc2, self.pre, tb=True)
+        ops.decode_cell_b16(self.pre, self.C2[0], self.C2[1], [self.H1[:, :R], self.H2[:, 2 * R:], self.hout], self.b2i, self.b2h)
+        self.C2.reverse()
+        ops.gemm(self.hout, W[21], self.logits, tb=True, bias=self.lg_b)
+        if normalize:
+            ops.log_softmax_rows_(self.logits)
+        return self.logits
 
     def _step_fused(self, it, alpha_out, normalize):
         S, R, A = self.S, self.R, self.A
@@ -1463,6 +1568,8 @@ class DecodeState:
     def step(self, it, alpha_out, normalize=True):
         if self.fused:
             return self._step_fused(it, alpha_out, normalize)
+        if self.b16:
+            return self._step_b16(it, alpha_out, normalize)
         S, R, A = self.S, self.R, self.A
         pr = self.pr
         if self.xt_table is not None:

@@ -123,6 +123,10 @@ class AttModel(CaptionModel):
         self.bf16_storage = str(g("compute_dtype", "fp32")).lower() in ("bf16", "bfloat16")
         if self.bf16_storage and (self.rnn_size % 8 or self.input_encoding_size % 8 or self.att_hid_size % 8 or self.GCN_dim % 8):
             raise ValueError("compute_dtype=bf16 needs rnn_size, input_encoding_size, att_hid_size and gcn_dim to be multiples of 8")
+        # opt-in (default 0), effective under compute_dtype = bf16 only: decode batches of more than 32 rows -- the image batch, beam
+        # search, forced decode, the self-critical rollout -- run their products on bf16 operands too (functions.DecodeState,
+        # regime "bf16-batched"); 0 keeps them on the fp32 step.  Not a reference option.
+        self.decode_b16_batched = int(g("decode_b16_batched", 0) or 0)
         # Full-GC only: compute the attention sets (att_embed / ctx2att over the node rows) ONCE per image and let the image's
         # sentences share them (functions.PreparedShared) instead of the reference's x5 replication (gcn_backbone.py:50-51 ->
         # AttModel.py:113-119).  That is the reference's arithmetic exactly when att_embed's Dropout is inactive (eval mode,
@@ -676,6 +680,10 @@ class AttModel(CaptionModel):
             return None
         flat16 = self.weights_b16()
         return [self.W16(n, flat16) for n in F_.PARAM_ORDER]
+
+    def decode_b16_on(self):
+        """True when decode states of more than 32 rows take the bf16-batched regime: the option is set and bf16 storage is on."""
+        return bool(getattr(self, "decode_b16_batched", 0)) and self.bf16_storage
 
     def invalidate_decode_caches(self):
         self.__dict__["_cache_epoch"] = self.__dict__.get("_cache_epoch", 0) + 1

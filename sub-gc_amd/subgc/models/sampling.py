@@ -237,7 +237,7 @@ class _GraphedLoop:
         if fb is not None:
             e = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)
             self.ro_sel, self.h_sel, self.fc_sel, self.idx_sel = e(n, 2 * L), e(n, A), e(n, 2 * L), e(n, N, dt=torch.long)
-        self.st = F_.DecodeState(self.pr, P, N, return_att, xt_table=m.xt_gates_table(), fuse_lstm=True, snapshots=m.decode_snapshots(), W16=m.decode_w16())
+        self.st = F_.DecodeState(self.pr, P, N, return_att, xt_table=m.xt_gates_table(), fuse_lstm=True, snapshots=m.decode_snapshots(), W16=m.decode_w16(), b16_batched=m.decode_b16_on())
         self.AL = z(T + 1, n, N) if return_att else None
         self.u = z(T, n) if k else None
         self.topk_temp = m.topk_temp
@@ -309,7 +309,9 @@ class _GraphedBeam:
             e = lambda *s, dt=torch.float32: torch.empty(*s, device=dev, dtype=dt)
             self.score_out, self.keep_out = e(n), z(n, dt=torch.long)
             self.ro_sel, self.h_sel, self.fc_sel, self.idx_sel = e(n, 2 * L), e(n, A), e(n, 2 * L), e(n, N, dt=torch.long)
-        self.eng = beam._BatchEngine(self.pr, P, N, int(opt.get("beam_size", 10)), m.xt_gates_table(), m.decode_snapshots(), return_att=return_att)
+        b16 = m.decode_b16_on()                                                  # on: the bf16 twins reach the engine (<= 32 rows: the fused bf16 regimes)
+        self.eng = beam._BatchEngine(self.pr, P, N, int(opt.get("beam_size", 10)), m.xt_gates_table(), m.decode_snapshots(), return_att=return_att,
+                                     W16=m.decode_w16() if b16 else None, b16_batched=b16)
         self.ds = beam.DeviceSearch(self.eng, T, opt, return_att)
         self._loop()                                                             # eager warm-up
         torch.cuda.synchronize()
@@ -330,9 +332,15 @@ class _GraphedBeam:
         return self.ds.collect()
 
 
+def _beam_graph_rows(m):
+    """The most beam rows (sub-graphs x beam) a captured search takes: 128, and 32 with decode_b16_batched on -- the bf16-batched regime
+    (> 32 rows) is not captured, it runs eagerly."""
+    return 32 if m.decode_b16_on() else 128
+
+
 def _graphed_beam(m, n, N, P, opt, fb=None, return_att=False):
     okey = tuple(sorted((k, v) for k, v in opt.items() if k in ("beam_size", "group_size", "diversity_lambda", "decoding_constraint", "length_penalty")))
-    okey += (("return_att", bool(return_att)),)
+    okey += (("return_att", bool(return_att)), ("b16_batched", m.decode_b16_on()))
     key = ("beam", n, N, okey, None if fb is None else fb.G) + m.weights_version()
     cache = m.__dict__.setdefault("_graph_cache", {})
     if key not in cache:
@@ -346,7 +354,7 @@ def _graphed_beam(m, n, N, P, opt, fb=None, return_att=False):
 
 def _graphed_loop(m, n, N, k, return_att, P, fb=None):
     top_p = m.the_p if k else 1.0
-    key = (n, N, (k, top_p), return_att, None if fb is None else fb.G) + m.weights_version()
+    key = (n, N, (k, top_p, m.decode_b16_on()), return_att, None if fb is None else fb.G) + m.weights_version()
     cache = m.__dict__.setdefault("_graph_cache", {})
     if key not in cache:
         for old in [q for q in cache if q[:5] == key[:5]]:                       # parameters changed: drop the stale snapshot
@@ -407,7 +415,7 @@ def decode_one_image(m, X2, N, image, opt, uniforms=None, forced=None):
         ops.decode_batch_finish(seq, seqlp, [0, n])
         return (seq, seqlp, score_out[:n], keep_out[:n])
     n = int(fr.n_keep.item())
-    if n == 0 or (beam_size > 1 and n * beam_size > 128) or (beam_size <= 1 and n > 16):
+    if n == 0 or (beam_size > 1 and n * beam_size > _beam_graph_rows(m)) or (beam_size <= 1 and n > 16):
         return decode(m, X2, N, select_subgraphs(m, X2, N, [image], front=fr, kept=[n]), opt, uniforms, forced)[0]
     P = m._decoder_params()
     try:
@@ -486,7 +494,7 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
         bounds.append(bounds[-1] + s)
     if beam_size > 1:                                                                  # AttModel.py:245-246 -> :179-234
         graphed = None
-        if len(sel) == 1 and n * beam_size <= 128 and getattr(m, "decode_hipgraph", True):
+        if len(sel) == 1 and n * beam_size <= _beam_graph_rows(m) and getattr(m, "decode_hipgraph", True):
             try:
                 graphed = _graphed_beam(m, n, N, P, opt, return_att=return_att)
             except RuntimeError as e:                                            # capture unavailable here: same kernels, launched eagerly
@@ -496,7 +504,9 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
         if graphed is not None:
             res = graphed.run(pr)
         else:
-            res = beam.beam_decode(pr, P, N, T, opt, xt_table=m.xt_gates_table(), return_att=return_att)
+            b16 = m.decode_b16_on()
+            res = beam.beam_decode(pr, P, N, T, opt, xt_table=m.xt_gates_table(), return_att=return_att, W16=m.decode_w16() if b16 else None,
+                                   b16_batched=b16)
         seq, seqlp, done = res[:3]
         m.done_beams = done if len(sel) == 1 else [done[a:b] for a, b in zip(bounds, bounds[1:])]
         AL = res[3]["AL"] if return_att else None
@@ -530,7 +540,7 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
     if graphed is not None:
         seq, seqlp, counts, AL, _, _ = graphed.run(pr, uniforms, step_major=own_u)
     else:
-        st = F_.DecodeState(pr, P, N, return_att, xt_table=m.xt_gates_table(), fuse_lstm=True, snapshots=m.decode_snapshots(), W16=m.decode_w16())
+        st = F_.DecodeState(pr, P, N, return_att, xt_table=m.xt_gates_table(), fuse_lstm=True, snapshots=m.decode_snapshots(), W16=m.decode_w16(), b16_batched=m.decode_b16_on())
         seq, seqlp, it = z(n, T, dt=torch.long), z(n, T), z(n, dt=torch.long)
         unfinished, counts = z(n, dt=torch.int32), z(T, dt=torch.int32)
         AL = z(T + 1, n, N) if return_att else None

@@ -11,7 +11,7 @@ import math
 
 import torch
 
-from ._lib import SubgcError, call, call_beam_att, call_consensus, call_criterion, call_selfcritical, lib
+from ._lib import SubgcError, call, call_beam_att, call_consensus, call_criterion, call_decode_b16, call_selfcritical, lib
 from . import _scoring
 
 RELU, ACCUM = 1, 2
@@ -1841,6 +1841,42 @@ def gather_rows_multi(pairs, rows):
         args += [_ptr(src, torch.float32), ld(src) if src is not None else 0, _ptr(dst, torch.float32), ld(dst) if dst is not None else 0,
                  dst.size(1) if dst is not None else 0]
     call("subgc_gather_rows_multi", len(pairs), *args, _ptr(rows, torch.int32), pairs[0][1].size(0), _stream())
+
+
+def decode_cell_b16(g0, c_prev, c, hs, b0=None, b1=None, table=None, tok=None, g2=None):
+    """One LSTM cell of the bf16-batched decode step (subgc_decode_cell_b16): pre = g0 + table[tok] + g2 + b0 + b1 in fp32, c fp32,
+    h rounded once to bf16 into the 1..3 views `hs` (each [S, R] bf16 with its own pitch)."""
+    S, R = c.shape
+    hs = list(hs)
+    if not 1 <= len(hs) <= 3:
+        raise SubgcError(f"decode_cell_b16 writes h to 1..3 destinations, got {len(hs)}")
+    if (table is None) != (tok is None):
+        raise SubgcError("decode_cell_b16: the x->gates table and the tokens come together")
+    if g0.size(0) < S or g0.size(1) != 4 * R or any(h_.size(0) < S or h_.size(1) != R for h_ in hs):
+        raise SubgcError(f"decode_cell_b16 shape mismatch: g0 {tuple(g0.shape)}, c {tuple(c.shape)}, h {[tuple(h_.shape) for h_ in hs]}")
+    if not (c.is_contiguous() and (c_prev is None or (c_prev.is_contiguous() and c_prev.shape == c.shape))):
+        raise SubgcError("decode_cell_b16: c and c_prev are contiguous [S, R]")
+    hp = []
+    for h_ in hs + [None] * (3 - len(hs)):
+        hp += [_ptr(h_, BF16), ld(h_) if h_ is not None else 0]
+    call_decode_b16("subgc_decode_cell_b16", _ptr(g0, torch.float32), ld(g0), _ptr(table, torch.float32), ld(table) if table is not None else 0,
+                    _ptr(tok, torch.int64), tok.stride(0) if tok is not None else 0, table.size(0) if table is not None else 0,
+                    _ptr(g2, torch.float32), ld(g2) if g2 is not None else 0, _ptr(b0, torch.float32), _ptr(b1, torch.float32),
+                    _ptr(c_prev, torch.float32), _ptr(c, torch.float32), *hp, len(hs), S, R, _stream())
+
+
+def decode_fork_b16(b16_pairs, f32_pairs, src):
+    """dst[m] = src_t[src[m]] for the two bf16 and the two fp32 (source, destination) pairs of the bf16-batched decode state in one launch
+    (subgc_decode_fork_b16); `src` int32 [S] on the device, no destination may overlap a source."""
+    if len(b16_pairs) != 2 or len(f32_pairs) != 2:
+        raise SubgcError("decode_fork_b16 moves two bf16 and two fp32 tensors")
+    S = src.numel()
+    args = []
+    for (a, b), dt in [(p, BF16) for p in b16_pairs] + [(p, torch.float32) for p in f32_pairs]:
+        if a.shape != b.shape or a.size(0) != S:
+            raise SubgcError(f"decode_fork_b16: {tuple(a.shape)} -> {tuple(b.shape)} with {S} rows")
+        args += [_ptr(a, dt), ld(a), _ptr(b, dt), ld(b), a.size(1)]
+    call_decode_b16("subgc_decode_fork_b16", *args, _ptr(src, torch.int32), S, _stream())
 
 
 def scatter_add_rows(src, rows, dX, m_dev=None):

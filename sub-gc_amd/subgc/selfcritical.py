@@ -146,7 +146,8 @@ def rollout(model, fc, Xb, lens, sel_idx, img_s, N, uniforms=None, T=None):
     two = lambda t: torch.cat([t, t]).contiguous()
     P = [p.detach() for p in model._decoder_params()]
     pr = F_.Prepared(two(fc.detach()), Xb.detach().contiguous(), two(lens), two(sel_idx), two(img_s), N, P, None, None, 1.0)
-    st = F_.DecodeState(pr, P, N, False, xt_table=model.xt_gates_table(), fuse_lstm=True, snapshots=model.decode_snapshots(), W16=model.decode_w16())
+    st = F_.DecodeState(pr, P, N, False, xt_table=model.xt_gates_table(), fuse_lstm=True, snapshots=model.decode_snapshots(), W16=model.decode_w16(),
+                        b16_batched=model.decode_b16_on())
     if uniforms is None:
         model.__dict__["_sample_calls"] = model.__dict__.get("_sample_calls", 0) + 1
         seed = (int(torch.initial_seed()) * 1000003 + model.__dict__["_sample_calls"]) & 0xFFFFFFFFFFFFFFFF
