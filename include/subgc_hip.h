@@ -1055,6 +1055,9 @@ typedef struct SubgcRecurrence {
     float* dC1_out;
     float* dC2_in;
     float* dC2_out;
+    int32_t zero_state;          /* 1: the state entering step 0 is zero (init_hidden) and its gradient is unused -- step 0 forms no product against it
+                                  * (forward: plain cell for the attention LSTM, K = 2R for the language LSTM, backward: PA has 2R columns, no PC),
+                                  * 0: every step issues the same launches */
 } SubgcRecurrence;
 int subgc_recurrence_sizeof(void);      /* sizeof(SubgcRecurrence): bindings that mirror the struct check their layout against it */
 /* forward: steps 0 .. T-1 in order.  workspace / ws_bytes: the split-K scratch of the cell products (as subgc_lstm_fwd_gemm). */

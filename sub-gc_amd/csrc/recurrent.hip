@@ -60,8 +60,13 @@ int fwd_step(const SubgcRecurrence* a, int t, void* workspace, size_t ws_bytes, 
     char* const H2n = at(a->H2, o1 * a->ldH2, esz);
     float* const C1p = a->C1 + (int64_t)t * S * R;
     float* const C2p = a->C2 + (int64_t)t * S * R;
+    // The state entering step 0 is zero (init_hidden): with `zero_state` its products are not formed.  The attention LSTM's whole
+    // product is [0 | 0] . Wc1^T, so the plain cell sums x->gates + fc->gates + biases; the language LSTM drops the h2_{-1} third of K.
+    const bool z0 = a->zero_state && t == 0;
     // attention LSTM: [h2_{t-1} | h1_{t-1}] . Wc1^T + x->gates + fc->gates; h1_t -> H2[t][:, R:2R] and the next step's H1[:, R:]
-    int rc = subgc_lstm_fwd_gemm(H1t, a->ldH1, a->Wc1, a->ldW1, 2 * R, a->pre, R4, a->Gx + o * R4, R4, a->Gf, R4, a->b1i, a->b1h, C1p,
+    int rc = z0 ? subgc_lstm_fwd(a->Gx + o * R4, R4, a->Gf, R4, nullptr, 0, a->b1i, a->b1h, C1p, C1p + (int64_t)S * R, H2t + (int64_t)R * esz, a->ldH2,
+                                 H1n + (int64_t)R * esz, a->ldH1, nullptr, 1.f, nullptr, 0, a->G1 + o * R4, m, R, m, mn, (cell_bits >> 1) & 1, stream)
+                : subgc_lstm_fwd_gemm(H1t, a->ldH1, a->Wc1, a->ldW1, 2 * R, a->pre, R4, a->Gx + o * R4, R4, a->Gf, R4, a->b1i, a->b1h, C1p,
                                  C1p + (int64_t)S * R, H2t + (int64_t)R * esz, a->ldH2, H1n + (int64_t)R * esz, a->ldH1, nullptr, 1.f, nullptr, 0,
                                  a->G1 + o * R4, m, R, m, mn, cell_bits, a->gemm_flags, workspace, ws_bytes, stream);
     if (rc != SUBGC_OK) return rc;
@@ -79,7 +84,7 @@ int fwd_step(const SubgcRecurrence* a, int t, void* workspace, size_t ws_bytes, 
                                       a->AL + o * a->n_alpha, a->n_alpha, m, A, R, attn_bits, stream);
     if (rc != SUBGC_OK) return rc;
     // language LSTM: [ctx_t | h1_t | h2_{t-1}] . Wc2^T; h2_t -> the next step's H1[:, :R] and H2[:, 2R:], dropout(h2_t) -> Hout
-    rc = subgc_lstm_fwd_gemm(H2t, a->ldH2, a->Wc2, a->ldW2, 3 * R, a->pre, R4, nullptr, 0, nullptr, 0, a->b2i, a->b2h, C2p, C2p + (int64_t)S * R,
+    rc = subgc_lstm_fwd_gemm(H2t, a->ldH2, a->Wc2, a->ldW2, (z0 ? 2 : 3) * R, a->pre, R4, nullptr, 0, nullptr, 0, a->b2i, a->b2h, C2p, C2p + (int64_t)S * R,
                              H1n, a->ldH1, H2n + 2 * (int64_t)R * esz, a->ldH2, a->k_out ? a->k_out + (int64_t)t * S * R : nullptr, a->keep_scale,
                              at(a->Hout, a->hout_off[t], esz), a->ld_hout, a->G2 + o * R4, m, R, mn, mn, cell_bits, a->gemm_flags, workspace,
                              ws_bytes, stream);
@@ -151,10 +156,13 @@ int bwd_step(const SubgcRecurrence* a, BwdState& st, int t, void* stream) {
                                        st.c2_in, dP2t, st.c2_out, m, R, a->bf16, stream);
         if (rc != SUBGC_OK) return rc;
     }
+    // `zero_state`: nothing reads the gradient of the initial state, so step 0 forms neither the dh2_prev third of PA nor PC
+    const bool z0 = a->zero_state && t == 0;
+    const int nA = (z0 ? 2 : 3) * R;
     int n = 0;
-    int rc = planes(dP2t, R4, (int)R4, a->Wc2, a->ldW2, 3 * R, m, a->PA, a->pa_bytes, &n);      // -> [dctx | dh1 | dh2_prev]
+    int rc = planes(dP2t, R4, (int)R4, a->Wc2, a->ldW2, nA, m, a->PA, a->pa_bytes, &n);         // -> [dctx | dh1 | dh2_prev]
     if (rc != SUBGC_OK) return rc;
-    st.sA = Win{a->PA, 3 * (int64_t)R, n, (int64_t)m * 3 * R, m};
+    st.sA = Win{a->PA, (int64_t)nA, n, (int64_t)m * nA, m};
     float* const keep = a->dv ? nullptr : a->dCtx + o * R;
     rc = a->shared ? subgc_attn_bwd_group(a->u, a->v, a->AH + o * A, a->w_a, a->rows_map, a->lens, m, a->B, a->g, a->Nn, a->AL + o * a->n_alpha,
                                           a->n_alpha, st.sA.p, st.sA.ld, dAHt, a->du, a->dWa + o * A, a->dBa + o, A, R, dbits, keep, R, st.sA.n, st.sA.stride,
@@ -180,6 +188,7 @@ int bwd_step(const SubgcRecurrence* a, BwdState& st, int t, void* stream) {
                                    0, nullptr, 1.f, st.c1_in, dP1t, st.c1_out, m, R, a->bf16, stream);
         if (rc != SUBGC_OK) return rc;
     }
+    if (z0) return SUBGC_OK;
     rc = planes(dP1t, R4, (int)R4, a->Wc1, a->ldW1, 2 * R, m, a->PC, a->pc_bytes, &n);          // -> [dh2_prev | dh1_prev]
     if (rc != SUBGC_OK) return rc;
     st.sC = Win{a->PC, 2 * (int64_t)R, n, (int64_t)m * 2 * R, m};

@@ -692,6 +692,36 @@ def grads_ready(stage):
     if on_grads_ready is not None:
         on_grads_ready(stage)
 
+
+# The recurrent weight gradients under ops.ZERO_STATE_SKIP (both decoder backwards).  The products whose x operand is a previous state
+# (h2_{t-1}, h1_{t-1}) skip the rows of step 0, where that operand is the zero initial state; a bias sum must still cover EVERY row of
+# dy, so it rides a product of the same dy that keeps all rows, and the twin bias (b_ih and b_hh have one gradient) gets the same values.
+def wgrad_twin_bias(out_for, acc, i, dy, x, b0, b1, cols=None):
+    """dW_i[:, cols] (+)= dy^T x over all rows; db_b0 and db_b1 (+)= ONE set of column sums of dy."""
+    o = out_for(i)
+    o = o if cols is None else o[:, cols[0]:cols[1]]
+    if FOLD_BIAS_SUMS:
+        tmp = torch.empty(dy.size(1), device=dy.device, dtype=torch.float32)
+        ops.wgrad(dy, x, o, tmp, accum=acc[i])
+    else:
+        ops.gemm(dy, x, o, ta=True, accum=acc[i])
+        tmp = ops.colsum(dy)
+    for j in (b0, b1):
+        ops.copy2d(tmp.view(1, -1), out_for(j).view(1, -1), accumulate=acc[j])
+
+
+def wgrad_after(out_for, acc, i, dy, x, r0, cols=None):
+    """dW_i[:, cols] (+)= dy[r0:]^T x[r0:]: the first r0 rows of x are the zero initial state and add nothing."""
+    o = out_for(i)
+    o = o if cols is None else o[:, cols[0]:cols[1]]
+    if dy.size(0) > r0:
+        ops.gemm(dy[r0:], x[r0:], o, ta=True, accum=acc[i])
+    else:
+        # no row after step 0 (every sentence ends there): exactly zero, or exactly untouched when accumulating -- the wgrad entry
+        # points' no-rows form; its bias operand accumulates nothing into a scratch vector
+        ops.wgrad(dy[r0:], x[r0:], o, torch.empty(dy.size(1), device=dy.device, dtype=torch.float32), accum=acc[i], db_accum=True)
+
+
 PARAM_ORDER = (
     "fc_embed.0.weight", "fc_embed.0.bias", "fc_embed.2.weight", "fc_embed.2.bias",
     "att_embed.0.weight", "att_embed.0.bias", "ctx2att.weight", "ctx2att.bias", "embed.0.weight",
@@ -1017,7 +1047,7 @@ class DecoderFn(Function):
                                  H1=H1, ldH1=H1.stride(1), H2=H2, ldH2=H2.stride(1), Hout=Hout, Wc1=Wc1, ldW1=ops.ld(Wc1), Wc2=Wc2, ldW2=ops.ld(Wc2),
                                  Wq=W[17], ldWq=ops.ld(W[17]), b1i=b1i, b1h=b1h, b2i=b2i, b2h=b2h, bq=h2a_b, pre=pre, Gx=Gx, Gf=Gf, C1=C1, C2=C2,
                                  G1=G1, G2=G2, AH=AH, AL=AL, k_out=k_out, QP=QP, qp_bytes=QP.numel() * 4, w_a=an_w, b_a=an_b, lens=lens,
-                                 **pr.recur_fields())
+                                 zero_state=int(ops.ZERO_STATE_SKIP), **pr.recur_fields())
             ops.recurrence_fwd(rec, H1)
         for t in range(T if rec is None else 0):
             if ss is not None:
@@ -1026,11 +1056,17 @@ class DecoderFn(Function):
                     ops.multinomial_rows_(logits3[:, t - 1, :], ss[2][t], ss[1][t], ss[0], tokens[:, t])
                 ops.embed_fwd(emb, tokens[:, t], tokens.stride(0), None if k_xt is None else k_xt[t], scale, xt[t])
                 ops.gemm(xt[t], W[9][:, 2 * R:], Gx3[t], tb=True)
-            ops.lstm_fwd_gemm(H1[t], Wc1, pre, Gx3[t], Gf, b1i, b1h, C1[t], C1[t + 1], H2[t][:, R:2 * R], H1[t + 1][:, R:], None, 1.0, None,
-                              G1[t], S, R)
+            z0 = ops.ZERO_STATE_SKIP and t == 0                 # the state entering step 0 is zero: no product against it (recurrent.hip)
+            if z0:
+                ops.lstm_fwd(Gx3[t], Gf, None, b1i, b1h, C1[t], C1[t + 1], H2[t][:, R:2 * R], H1[t + 1][:, R:], None, 1.0, None, G1[t], S, R,
+                             rows_h=S, rows_h2=S)
+            else:
+                ops.lstm_fwd_gemm(H1[t], Wc1, pre, Gx3[t], Gf, b1i, b1h, C1[t], C1[t + 1], H2[t][:, R:2 * R], H1[t + 1][:, R:], None, 1.0, None,
+                                  G1[t], S, R)
             nq, sq = ops.gemm_planes(H2[t][:, R:2 * R], W[17], QP, tb=True)      # the query product stays as split-K planes: the attention
             pr.attn_fwd(AH[t], an_w, an_b, lens, H2[t][:, :R], AL[t], S, A, R, q=(QP, nq, sq, h2a_b))     # kernel sums them (+ bias) into AH[t]
-            ops.lstm_fwd_gemm(H2[t], Wc2, pre, None, None, b2i, b2h, C2[t], C2[t + 1], H1[t + 1][:, :R], H2[t + 1][:, 2 * R:],
+            kz = 2 * R if z0 else 3 * R
+            ops.lstm_fwd_gemm(H2[t][:, :kz], Wc2[:, :kz], pre, None, None, b2i, b2h, C2[t], C2[t + 1], H1[t + 1][:, :R], H2[t + 1][:, 2 * R:],
                               None if k_out is None else k_out[t], scale, Hout[:, t, :], G2[t], S, R)
         if ss is None:
             ops.gemm(ops.flat_rows(Hout), W[21], logits, tb=True, bias=lg_b)
@@ -1166,7 +1202,7 @@ class DecoderFn(Function):
                                  du_planes=du.size(0) if du.dim() == 3 else 1, du_plane_stride=du.stride(0) if du.dim() == 3 else 0,
                                  dv=None if defer_dv else dv, dWa=dWa, dBa=dBa, dCtx=dCtx if defer_dv else None, dE=dE, PA=PA, pa_bytes=PA.numel() * 4,
                                  PB=PB, pb_bytes=PB.numel() * 4, PC=PC, pc_bytes=PC.numel() * 4, dC1_in=dC1[0], dC1_out=dC1[1], dC2_in=dC2[0],
-                                 dC2_out=dC2[1], **pr.recur_fields())
+                                 dC2_out=dC2[1], zero_state=int(ops.ZERO_STATE_SKIP), **pr.recur_fields())
             ops.recurrence_bwd(rec)
         for t in range(T - 1, -1, -1):
             if rec is not None:
@@ -1174,14 +1210,17 @@ class DecoderFn(Function):
             nC1, cC1 = dC1; nC2, cC2 = dC2
             ops.lstm_bwd_planes(G2[t], C2[t], C2[t + 1], [win(sC, 0), win(sA, 2 * R)], dHout[:, t, :], None if k_out is None else k_out[t],
                                 scale, nC2, dP2[t], cC2, S, R)
-            n, st = ops.gemm_planes(dP2[t], Wc2, PA)                       # -> [dctx | dh1 | dh2_prev]
-            sA = (PA, 3 * R, n, st, S)
+            z0 = ops.ZERO_STATE_SKIP and t == 0                 # the initial state's gradient is unused: no dh2_prev third of PA, no PC
+            nA = 2 * R if z0 else 3 * R
+            n, st = ops.gemm_planes(dP2[t], Wc2[:, :nA], PA)               # -> [dctx | dh1 | dh2_prev]
+            sA = (PA, nA, n, st, S)
             pr.attn_bwd(AH[t], an_w, lens, AL[t], win(sA, 0), dAH[t], du, None if defer_dv else dv, dWa[t], dBa[t], S, A, R,
                         dCtx[t] if defer_dv else None, **({"de_keep": dE[t]} if defer_du else {}))
             n, st = ops.gemm_planes(dAH[t], W[17], PB)                     # h1 also feeds the attention query
             ops.lstm_bwd_planes(G1[t], C1[t], C1[t + 1], [win(sA, R), (PB, R, 0, n, st, S), win(sC, R)], None, None, 1.0, nC1, dP1[t], cC1, S, R)
-            n, st = ops.gemm_planes(dP1[t], Wc1, PC)                       # -> [dh2_prev | dh1_prev]
-            sC = (PC, 2 * R, n, st, S)
+            if not z0:
+                n, st = ops.gemm_planes(dP1[t], Wc1, PC)                   # -> [dh2_prev | dh1_prev]
+                sC = (PC, 2 * R, n, st, S)
             dC1.reverse(); dC2.reverse()
         note("bptt_end")
 
@@ -1193,13 +1232,23 @@ class DecoderFn(Function):
             del dE
         P1, P2 = dP1.view(T * S, 4 * R), dP2.view(T * S, 4 * R)
         H1a, H2a = ops.flat_rows(H1[:T]), ops.flat_rows(H2[:T])
-        wgrad(13, P2, H2a[:, :2 * R], bias=15)             # b_ih and b_hh have the same gradient: one sum rides each product
-        wgrad(14, P2, H2a[:, 2 * R:], bias=16)
-        wgrad(9, P1, H1a[:, :R], cols=(0, R), bias=11)
+        zs = ops.ZERO_STATE_SKIP                                # the S rows of step 0 of the previous-state operands are the zero initial state
+        if zs:
+            wgrad_twin_bias(out_for, acc, 13, P2, H2a[:, :2 * R], 15, 16)
+            wgrad_after(out_for, acc, 14, P2, H2a[:, 2 * R:], S)
+            wgrad_after(out_for, acc, 9, P1, H1a[:, :R], S, cols=(0, R))
+        else:
+            wgrad(13, P2, H2a[:, :2 * R], bias=15)         # b_ih and b_hh have the same gradient: one sum rides each product
+            wgrad(14, P2, H2a[:, 2 * R:], bias=16)
+            wgrad(9, P1, H1a[:, :R], cols=(0, R), bias=11)
         dGf = opnd(ops.colsum(dP1.view(T, S * 4 * R)).view(S, 4 * R))
         wgrad(9, dGf, pr.f16 if bf else pr.f, cols=(R, 2 * R))
-        wgrad(9, P1, xt.view(T * S, E), cols=(2 * R, 2 * R + E))
-        wgrad(10, P1, H1a[:, R:], bias=12)
+        if zs:
+            wgrad_twin_bias(out_for, acc, 9, P1, xt.view(T * S, E), 11, 12, cols=(2 * R, 2 * R + E))
+            wgrad_after(out_for, acc, 10, P1, H1a[:, R:], S)
+        else:
+            wgrad(9, P1, xt.view(T * S, E), cols=(2 * R, 2 * R + E))
+            wgrad(10, P1, H1a[:, R:], bias=12)
         df = new(S, R); ops.gemm(dGf, W[9][:, R:2 * R], df)
         dxt = new(T * S, E); ops.gemm(P1, W[9][:, 2 * R:], dxt)
         d_emb = out_for(8, zero=True)

@@ -143,7 +143,8 @@ class PackedDecoderLossFn(Function):
                                  hout_off=[o_ * ops.ld(Hout) for o_ in ot[:T_live]], ld_hout=ops.ld(Hout), H1=H1, ldH1=ops.ld(H1), H2=H2,
                                  ldH2=ops.ld(H2), Hout=Hout, Wc1=Wc1, ldW1=ops.ld(Wc1), Wc2=Wc2, ldW2=ops.ld(Wc2), Wq=W[17], ldWq=ops.ld(W[17]),
                                  b1i=b1i, b1h=b1h, b2i=b2i, b2h=b2h, bq=h2a_b, pre=pre, Gx=Gx, Gf=Gf, C1=C1, C2=C2, G1=G1, G2=G2, AH=AH, AL=AL,
-                                 k_out=k_out, QP=QP, qp_bytes=QP.numel() * 4, w_a=an_w, b_a=an_b, lens=lens_p, **pr.recur_fields())
+                                 k_out=k_out, QP=QP, qp_bytes=QP.numel() * 4, w_a=an_w, b_a=an_b, lens=lens_p, zero_state=int(ops.ZERO_STATE_SKIP),
+                                 **pr.recur_fields())
             ops.recurrence_fwd(rec, H1)
         for t in range(T_live if rec is None else 0):
             m, o, mn = M[t], ot[t], (M[t + 1] if t + 1 < T else 0)
@@ -156,12 +157,18 @@ class PackedDecoderLossFn(Function):
                     ops.multinomial_rows_(logits[op:op + m], u_p[t][:m], sel_p[t][:m], ss[0], tok_flat[o:o + m])
                 ops.embed_fwd(emb, tok_flat[o:o + m], 1, None if k_flat is None else k_flat[o:o + m], scale, xt[o:o + m])
                 ops.gemm(xt[o:o + m], W[9][:, 2 * R:], Gx[o:o + m], tb=True)
-            ops.lstm_fwd_gemm(H1[o:o + m], Wc1, pre[:m], Gx[o:o + m], Gf[:m], b1i, b1h, C1[t][:m], C1[t + 1][:m], H2[o:o + m, R:2 * R],
-                              H1[o1:o1 + mn_, R:], None, 1.0, None, G1[o:o + m], m, R, rows_h=m, rows_h2=mn_)
+            z0 = ops.ZERO_STATE_SKIP and t == 0                 # the state entering step 0 is zero: no product against it (recurrent.hip)
+            if z0:
+                ops.lstm_fwd(Gx[o:o + m], Gf[:m], None, b1i, b1h, C1[t][:m], C1[t + 1][:m], H2[o:o + m, R:2 * R], H1[o1:o1 + mn_, R:], None, 1.0,
+                             None, G1[o:o + m], m, R, rows_h=m, rows_h2=mn_)
+            else:
+                ops.lstm_fwd_gemm(H1[o:o + m], Wc1, pre[:m], Gx[o:o + m], Gf[:m], b1i, b1h, C1[t][:m], C1[t + 1][:m], H2[o:o + m, R:2 * R],
+                                  H1[o1:o1 + mn_, R:], None, 1.0, None, G1[o:o + m], m, R, rows_h=m, rows_h2=mn_)
             nq, sq = ops.gemm_planes(H2[o:o + m, R:2 * R], W[17], QP, tb=True)   # the query product stays as split-K planes: the attention
             pr.attn_fwd(AH[o:o + m], an_w, an_b, lens_p, H2[o:o + m, :R], AL[o:o + m], m, A, R, q=(QP, nq, sq, h2a_b))   # kernel sums them (+ bias) into AH
 
-            ops.lstm_fwd_gemm(H2[o:o + m], Wc2, pre[:m], None, None, b2i, b2h, C2[t][:m], C2[t + 1][:m], H1[o1:o1 + mn_, :R],
+            kz = 2 * R if z0 else 3 * R
+            ops.lstm_fwd_gemm(H2[o:o + m, :kz], Wc2[:, :kz], pre[:m], None, None, b2i, b2h, C2[t][:m], C2[t + 1][:m], H1[o1:o1 + mn_, :R],
                               H2[o1:o1 + mn_, 2 * R:], None if k_out is None else k_out[t], scale, Hout[o:o + m], G2[o:o + m], m, R,
                               rows_h=mn_, rows_h2=mn_)
         if ss is None:
@@ -272,7 +279,8 @@ class PackedDecoderLossFn(Function):
                                  dP1=dP1, dP2=dP2, dAH=dAH, du=du, du_planes=du.size(0) if du.dim() == 3 else 1,
                                  du_plane_stride=du.stride(0) if du.dim() == 3 else 0, dv=None if defer_dv else dv, dWa=dWa, dBa=dBa,
                                  dCtx=dCtx if defer_dv else None, dE=dE, PA=PA, pa_bytes=PA.numel() * 4, PB=PB, pb_bytes=PB.numel() * 4, PC=PC,
-                                 pc_bytes=PC.numel() * 4, dC1_in=dC1[0], dC1_out=dC1[1], dC2_in=dC2[0], dC2_out=dC2[1], **pr.recur_fields())
+                                 pc_bytes=PC.numel() * 4, dC1_in=dC1[0], dC1_out=dC1[1], dC2_in=dC2[0], dC2_out=dC2[1], zero_state=int(ops.ZERO_STATE_SKIP),
+                                 **pr.recur_fields())
             ops.recurrence_bwd(rec)
         for t in range(T_live - 1, -1, -1):
             if rec is not None:
@@ -281,22 +289,32 @@ class PackedDecoderLossFn(Function):
             nC1, cC1 = dC1; nC2, cC2 = dC2
             ops.lstm_bwd_planes(G2[o:o + m], C2[t][:m], C2[t + 1][:m], [win(sC, 0), win(sA, 2 * R)], dHout[o:o + m],
                                 None if k_out is None else k_out[t], scale, nC2[:m], dP2[o:o + m], cC2[:m], m, R)
-            n, st = ops.gemm_planes(dP2[o:o + m], Wc2, PA)
-            sA = (PA, 3 * R, n, st, m)
+            z0 = ops.ZERO_STATE_SKIP and t == 0                 # the initial state's gradient is unused: no dh2_prev third of PA, no PC
+            nA = 2 * R if z0 else 3 * R
+            n, st = ops.gemm_planes(dP2[o:o + m], Wc2[:, :nA], PA)
+            sA = (PA, nA, n, st, m)
             pr.attn_bwd(AH[o:o + m], an_w, lens_p, AL[o:o + m], win(sA, 0), dAH[o:o + m], du, None if defer_dv else dv,
                         dWa[o:o + m], dBa[o:o + m], m, A, R, dCtx[o:o + m] if defer_dv else None, **({"de_keep": dE[o:o + m]} if defer_du else {}))
             n, st = ops.gemm_planes(dAH[o:o + m], W[17], PB)
             ops.lstm_bwd_planes(G1[o:o + m], C1[t][:m], C1[t + 1][:m], [win(sA, R), (PB, R, 0, n, st, m), win(sC, R)], None, None, 1.0, nC1[:m],
                                 dP1[o:o + m], cC1[:m], m, R)
-            n, st = ops.gemm_planes(dP1[o:o + m], Wc1, PC)
-            sC = (PC, 2 * R, n, st, m)
+            if not z0:
+                n, st = ops.gemm_planes(dP1[o:o + m], Wc1, PC)
+                sC = (PC, 2 * R, n, st, m)
             dC1.reverse(); dC2.reverse()
         F_.note("bptt_end")
 
         P1, P2, H1a, H2a = dP1[:rows], dP2[:rows], H1[:rows], H2[:rows]
-        wgrad(13, P2, H2a[:, :2 * R], bias=15)             # b_ih and b_hh have the same gradient: one sum rides each product
-        wgrad(14, P2, H2a[:, 2 * R:], bias=16)
-        wgrad(9, P1, H1a[:, :R], cols=(0, R), bias=11)
+        zs = ops.ZERO_STATE_SKIP                                # the first M[0] rows of the previous-state operands are the zero initial state
+        r0 = M[0] if T_live > 0 else 0
+        if zs:
+            F_.wgrad_twin_bias(out_for, acc, 13, P2, H2a[:, :2 * R], 15, 16)
+            F_.wgrad_after(out_for, acc, 14, P2, H2a[:, 2 * R:], r0)
+            F_.wgrad_after(out_for, acc, 9, P1, H1a[:, :R], r0, cols=(0, R))
+        else:
+            wgrad(13, P2, H2a[:, :2 * R], bias=15)         # b_ih and b_hh have the same gradient: one sum rides each product
+            wgrad(14, P2, H2a[:, 2 * R:], bias=16)
+            wgrad(9, P1, H1a[:, :R], cols=(0, R), bias=11)
         step_off = plan.offs                                    # int32 [T+1] on the device; steps past T_live repeat `rows`
         if defer_dv:
             pr.dv_accum(AL, dCtx, step_off, max(T_live, 1), lens_p, dv, S, R)
@@ -308,8 +326,12 @@ class PackedDecoderLossFn(Function):
         ops.packed_time_sum(dP1, step_off, T_live, S, dGf)
         dGf = opnd(dGf)
         wgrad(9, dGf, pr.f16 if bf else pr.f, cols=(R, 2 * R))
-        wgrad(9, P1, xt[:rows], cols=(2 * R, 2 * R + E))
-        wgrad(10, P1, H1a[:, R:], bias=12)
+        if zs:
+            F_.wgrad_twin_bias(out_for, acc, 9, P1, xt[:rows], 11, 12, cols=(2 * R, 2 * R + E))
+            F_.wgrad_after(out_for, acc, 10, P1, H1a[:, R:], r0)
+        else:
+            wgrad(9, P1, xt[:rows], cols=(2 * R, 2 * R + E))
+            wgrad(10, P1, H1a[:, R:], bias=12)
         df = new(S, R); ops.gemm(dGf, W[9][:, R:2 * R], df)
         dxt = new(max(rows, 1), E); ops.gemm(P1, W[9][:, 2 * R:], dxt[:rows])
         d_emb = out_for(8, zero=True)

@@ -1029,6 +1029,10 @@ def gemm_planes(a, b, planes, *, ta=False, tb=False):
 
 
 RECURRENCE_IN_C = True        # the train decoder's T-step loops as one C call per direction (subgc_recurrence_fwd / _bwd); False = step by step from Python
+# The state entering step 0 of the train decoder is zero (init_hidden) and nothing reads its gradient: step 0 then forms no product
+# against it (SubgcRecurrence.zero_state and the same launches in the Python loops), and the weight gradients whose x operand is a
+# previous state contract over the rows after step 0 only.  False = every step issues the same launches.
+ZERO_STATE_SKIP = True
 _RECUR_T = None
 
 
