@@ -624,7 +624,12 @@ int subgc_pick_lse_finish(const float* lse_part, int V, int S, int T, const int3
  *   subgc_attn_group_du_planes(g) workgroups (1 or 2: a second wave per SIMD hides the tanh chains' latency); each accumulates into
  *   its own d(u) plane du + p * du_plane_stride -- the caller zeroes du_planes planes and adds them after the last step.
  *   dv_accum: dv [B*Nn, R] = sum over steps t and live sentences of alpha_t[row, i] * dctx_t[row, :]; step t's rows start at
- *   step_off[t] with step_off[t+1] - step_off[t] of them live (every row of dv is written).                                      */
+ *   step_off[t] with step_off[t+1] - step_off[t] of them live (every row of dv is written).
+ *   Finite rows: the node rows of u and v below the image's longest live set (rows i < max over its live sentences of lens) must be
+ *   finite.  The forward serves a sentence j shorter than that by weighting rows [lens_j, longest) with an exact zero, it does not skip
+ *   them, so a NaN or Inf there would reach ctx[row_j]; finite values there change no bit of sentence j's results.  Rows at or beyond the
+ *   longest live set are never read.  (The bound is conservative: a workgroup reads up to the longest set among the sentences IT serves,
+ *   which for an image split over two workgroups may be shorter than the image's.)                                              */
 int subgc_attn_fwd_group(const void* u, const void* v, const float* ah, const float* w_a, const float* b_a, const int32_t* rows,
                          const int32_t* lens, int m, int B, int g, int Nn, void* ctx, int64_t ldctx, float* alpha, int n_stride, int A,
                          int R, int bf16_bits, void* stream);
