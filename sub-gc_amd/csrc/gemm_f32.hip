@@ -25,6 +25,8 @@
 #include "bf16_util.h"
 
 #include <algorithm>
+#include "../../include/subgc_gcn_agg_hip.h"
+
 #include <cstdlib>
 #include <type_traits>
 #include <utility>
@@ -53,6 +55,9 @@ struct GemmArgs {
     // subgc_gemm_f32_pair: a SECOND problem of the same shape, layout and epilogue in the same launch (the second half of the grid)
     const float* A2 = nullptr; const float* B2 = nullptr; float* C2 = nullptr; const float* bias2 = nullptr;
     int nprob = 1;
+    // subgc_gemm_f32_rowbias / _pair_rowbias: the bias of row m enters as bscale[m] * bias (a bias under a row-normalised 0/1 aggregation);
+    // NULL = the plain bias, bit for bit
+    const float* bscale = nullptr; const float* bscale2 = nullptr;
 };
 
 // Pair launches (see gemm_bf16.hip): workgroups [0, nwg/2) work on problem 0, [nwg/2, nwg) on problem 1
@@ -61,7 +66,7 @@ __device__ __forceinline__ int select_problem(GemmArgs& q, int& b, int& nwg) {
     nwg >>= 1;
     if (b < nwg) return 0;
     b -= nwg;
-    q.A = q.A2; q.B = q.B2; q.C = q.C2; q.bias = q.bias2;
+    q.A = q.A2; q.B = q.B2; q.C = q.C2; q.bias = q.bias2; q.bscale = q.bscale2;
     return 1;
 }
 
@@ -453,7 +458,8 @@ __device__ __forceinline__ void epilogue(const GemmArgs& p, int M, int m0, int n
             row = g;
         }
         if (vec) {
-            if (p.bias) { const float4 t = ld4(p.bias + n); x.v[0] += t.x; x.v[1] += t.y; x.v[2] += t.z; x.v[3] += t.w; }
+            if (p.bias && p.bscale) { const float4 t = ld4(p.bias + n); const float bs = p.bscale[m]; x.v[0] += bs * t.x; x.v[1] += bs * t.y; x.v[2] += bs * t.z; x.v[3] += bs * t.w; }
+            else if (p.bias) { const float4 t = ld4(p.bias + n); x.v[0] += t.x; x.v[1] += t.y; x.v[2] += t.z; x.v[3] += t.w; }
             if (p.add) { const float4 t = ld4(p.add + row * p.ldadd + n); x.v[0] += t.x; x.v[1] += t.y; x.v[2] += t.z; x.v[3] += t.w; }
             if (relu) {
 #pragma unroll
@@ -473,7 +479,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& p, int M, int m0, int n
         for (int e = 0; e < 4; ++e) {
             const int col = n + e;
             if (col >= p.N) break;
-            float v = x.v[e] + (p.bias ? p.bias[col] : 0.f);
+            float v = x.v[e] + (p.bias ? (p.bscale ? p.bscale[m] * p.bias[col] : p.bias[col]) : 0.f);
             float* dst = p.C + row * p.ldc + col;
             if (p.add) v += p.add[row * p.ldadd + col];
             if (relu) v = fmaxf(v, 0.f);
@@ -608,9 +614,10 @@ __global__ __launch_bounds__(XM ? 512 : 256, XM >= 3 ? 2 : 1) void gemm_f32_spli
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ ws, int splits, int M, int N, float* __restrict__ C,
                                                             int64_t ldc, const float* __restrict__ bias, int accum, int vec,
                                                             const float* __restrict__ cs_part = nullptr, float* __restrict__ cs_out = nullptr, int cs_accum = 0,
-                                                            float* __restrict__ C2 = nullptr, const float* __restrict__ bias2 = nullptr) {
+                                                            float* __restrict__ C2 = nullptr, const float* __restrict__ bias2 = nullptr,
+                                                            const float* __restrict__ bscale = nullptr, const float* __restrict__ bscale2 = nullptr) {
     const size_t plane = (size_t)M * N;
-    if (blockIdx.y == 1) { ws += (size_t)splits * plane; C = C2; bias = bias2; }          // pair launch: grid.y = problem
+    if (blockIdx.y == 1) { ws += (size_t)splits * plane; C = C2; bias = bias2; bscale = bscale2; }          // pair launch: grid.y = problem
     if (cs_part != nullptr)                                      // the column sums of A that came with the weight gradient, parts added in order
         for (int m = blockIdx.x * blockDim.x + threadIdx.x; m < M; m += gridDim.x * blockDim.x) {
             float v = 0.f;
@@ -623,6 +630,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
             const int64_t row = i / n4;
             const int c4 = (int)(i - row * n4) * 4;
             float4 v = bias ? *reinterpret_cast<const float4*>(bias + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
+            if (bias && bscale) { const float bs = bscale[row]; v.x *= bs; v.y *= bs; v.z *= bs; v.w *= bs; }      // per-row bias scale (rowbias forms)
             for (int s = 0; s < splits; ++s) {
                 const float4 q = *reinterpret_cast<const float4*>(ws + s * plane + (size_t)row * N + c4);
                 v.x += q.x; v.y += q.y; v.z += q.z; v.w += q.w;
@@ -635,7 +643,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
         for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (int64_t)M * N; i += (int64_t)gridDim.x * blockDim.x) {
             const int64_t row = i / N;
             const int col = (int)(i - row * N);
-            float v = bias ? bias[col] : 0.f;
+            float v = bias ? (bscale ? bscale[row] * bias[col] : bias[col]) : 0.f;
             for (int s = 0; s < splits; ++s) v += ws[s * plane + (size_t)i];
             float* d = C + row * ldc + col;
             *d = accum ? *d + v : v;
@@ -730,7 +738,7 @@ int launch_splitk(const GemmArgs& a, hipStream_t s, int splits, bool reduce = tr
     const int64_t n = (int64_t)a.M * a.N / (vec ? 4 : 1);
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 2048), (unsigned)a.nprob), dim3(256), 0, s, (const float*)a.ws,
                        splits, a.M, a.N, a.C, a.ldc, a.bias, (a.flags & SUBGC_GEMM_ACCUM) ? 1 : 0, vec,
-                       with_cs ? (const float*)a.cs_part : nullptr, a.cs_out, a.cs_accum, a.C2, a.bias2);
+                       with_cs ? (const float*)a.cs_part : nullptr, a.cs_out, a.cs_accum, a.C2, a.bias2, a.bscale, a.bscale2);
     return subgc::check_launch("subgc_gemm_f32(split-K)");
 }
 
@@ -800,6 +808,8 @@ int dispatch(const GemmArgs& a, int transA, int transB, bool vec, int flags, hip
                 if (a.add) tail.add = a.add + M1 * a.ldadd;
                 if (a.keep) tail.keep = a.keep + M1 * a.ldc;          // the mask shares the destination's leading dimension (epilogue)
                 if (a.nprob == 2) { tail.A2 = a.A2 + M1 * a.lda; tail.C2 = a.C2 + M1 * a.ldc; }
+                if (a.bscale) tail.bscale = a.bscale + M1;
+                if (a.bscale2) tail.bscale2 = a.bscale2 + M1;
                 int rc;
                 if (transB) rc = vec ? pick_tile<false, true, true>(head, s) : pick_tile<false, true, false>(head, s);
                 else rc = vec ? pick_tile<false, false, true>(head, s) : pick_tile<false, false, false>(head, s);
@@ -864,6 +874,55 @@ SUBGC_API int subgc_gemm_f32_pair(int transA, int transB, int M, int N, int K, c
     GemmArgs a{A1, B1, C1, bias1, nullptr, nullptr, nullptr, nullptr, nullptr, lda, ldb, ldc, 0, M, N, K, flags & 15, 1.f,
                static_cast<float*>(workspace), ws_bytes, mode_bits ? mode_bits - 1 : g_x3, (flags & SUBGC_GEMM_NO_SPLITK) ? 1 : 0};
     a.A2 = A2; a.B2 = B2; a.C2 = C2; a.bias2 = bias2; a.nprob = 2;
+    hipStream_t s = (hipStream_t)stream;
+    const bool vecA = aligned16(A1) && aligned16(A2) && lda % 4 == 0 && (transA ? M % 4 == 0 : K % 4 == 0);
+    const bool vecB = aligned16(B1) && aligned16(B2) && ldb % 4 == 0 && (transB ? K % 4 == 0 : N % 4 == 0);
+    subgc::ProfScope prof(SUBGC_FAM_GEMM, s, 4.0 * M * (double)N * K);
+    return dispatch(a, transA, transB, vecA && vecB, flags, s);
+}
+
+// The two entry points above with a per-row scale on the bias (include/subgc_gcn_agg_hip.h): C = epilogue(op(A) op(B) + bias_scale[row] * bias).
+// The scale travels in GemmArgs to the tile epilogue and to the split-K reduce pass; the row cut moves it with the rows.
+SUBGC_API int subgc_gemm_f32_rowbias(int transA, int transB, int M, int N, int K, const float* A, int64_t lda, const float* B, int64_t ldb, float* C,
+                                     int64_t ldc, const float* bias, const float* bias_scale, int flags, void* workspace, size_t ws_bytes,
+                                     void* stream) {
+    SUBGC_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm_f32_rowbias: negative size M=%d N=%d K=%d", M, N, K);
+    SUBGC_REQUIRE((workspace != nullptr || ws_bytes == 0) && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
+                  "gemm_f32_rowbias: workspace must be 16-byte aligned (NULL with 0 bytes = none)");
+    if (M == 0 || N == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(A && B && C, "gemm_f32_rowbias: null operand");
+    SUBGC_REQUIRE(!(transA && transB), "gemm_f32_rowbias: transA && transB not supported");
+    SUBGC_REQUIRE(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, "gemm_f32_rowbias: leading dimension too small");
+    SUBGC_REQUIRE(!bias_scale || bias, "gemm_f32_rowbias: a bias scale without a bias");
+    const int mode_bits = (flags >> 4) & 3;
+    GemmArgs a{A, B, C, bias, nullptr, nullptr, nullptr, nullptr, nullptr, lda, ldb, ldc, 0, M, N, K, flags & 15, 1.f,
+               static_cast<float*>(workspace), ws_bytes, mode_bits ? mode_bits - 1 : g_x3, (flags & SUBGC_GEMM_NO_SPLITK) ? 1 : 0};
+    a.bscale = bias_scale;
+    hipStream_t s = (hipStream_t)stream;
+    const bool vecA = aligned16(A) && lda % 4 == 0 && (transA ? M % 4 == 0 : K % 4 == 0);
+    const bool vecB = aligned16(B) && ldb % 4 == 0 && (transB ? K % 4 == 0 : N % 4 == 0);
+    subgc::ProfScope prof(SUBGC_FAM_GEMM, s, 2.0 * M * (double)N * K);
+    return dispatch(a, transA, transB, vecA && vecB, flags, s);
+}
+
+SUBGC_API int subgc_gemm_f32_pair_rowbias(int transA, int transB, int M, int N, int K, const float* A1, const float* A2, int64_t lda, const float* B1,
+                                          const float* B2, int64_t ldb, float* C1, float* C2, int64_t ldc, const float* bias1, const float* bias2,
+                                          const float* bias_scale1, const float* bias_scale2, int flags, void* workspace, size_t ws_bytes,
+                                          void* stream) {
+    SUBGC_REQUIRE(M >= 0 && N >= 0 && K >= 0, "gemm_f32_pair_rowbias: negative size M=%d N=%d K=%d", M, N, K);
+    SUBGC_REQUIRE((workspace != nullptr || ws_bytes == 0) && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0,
+                  "gemm_f32_pair_rowbias: workspace must be 16-byte aligned (NULL with 0 bytes = none)");
+    if (M == 0 || N == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(A1 && A2 && B1 && B2 && C1 && C2, "gemm_f32_pair_rowbias: null operand");
+    SUBGC_REQUIRE(!(transA && transB), "gemm_f32_pair_rowbias: transA && transB not supported");
+    SUBGC_REQUIRE(lda >= (transA ? M : K) && ldb >= (transB ? K : N) && ldc >= N, "gemm_f32_pair_rowbias: leading dimension too small");
+    SUBGC_REQUIRE((bias1 != nullptr) == (bias2 != nullptr), "gemm_f32_pair_rowbias: bias for both problems or for none");
+    SUBGC_REQUIRE((bias_scale1 != nullptr) == (bias_scale2 != nullptr) && (!bias_scale1 || bias1), "gemm_f32_pair_rowbias: bias scales for both biases or for none");
+    const int mode_bits = (flags >> 4) & 3;
+    GemmArgs a{A1, B1, C1, bias1, nullptr, nullptr, nullptr, nullptr, nullptr, lda, ldb, ldc, 0, M, N, K, flags & 15, 1.f,
+               static_cast<float*>(workspace), ws_bytes, mode_bits ? mode_bits - 1 : g_x3, (flags & SUBGC_GEMM_NO_SPLITK) ? 1 : 0};
+    a.A2 = A2; a.B2 = B2; a.C2 = C2; a.bias2 = bias2; a.nprob = 2;
+    a.bscale = bias_scale1; a.bscale2 = bias_scale2;
     hipStream_t s = (hipStream_t)stream;
     const bool vecA = aligned16(A1) && aligned16(A2) && lda % 4 == 0 && (transA ? M % 4 == 0 : K % 4 == 0);
     const bool vecB = aligned16(B1) && aligned16(B2) && ldb % 4 == 0 && (transB ? K % 4 == 0 : N % 4 == 0);
@@ -1259,4 +1318,62 @@ SUBGC_API int subgc_colsum_f32(const float* X, int64_t ldx, int M, int N, float*
     dim3 grid((N + 63) / 64, (M + rows_per_block - 1) / rows_per_block);
     hipLaunchKernelGGL(colsum_kernel, grid, dim3(256), 0, s, X, ldx, M, N, out, accumulate, m_dev, rows_per_block);
     return subgc::check_launch("subgc_colsum_f32");
+}
+
+// ---- row-weighted column sums (include/subgc_gcn_agg_hip.h): the bias gradients under aggregation, db = sum_i s[i] dY[i, :] ------------
+namespace {
+struct ColsumRows { const float* x[2]; const float* w[2]; float* out[2]; };
+inline int colsum_rows_rpb(int M, int N) { return std::max(16, (int)(((int64_t)M * ((N + 63) / 64) + 1023) / 1024)); }
+// block (column group of 64, slab, matrix): wave w adds rows r0 + w, r0 + w + 4, ... (four requested at a time, added in that order), the four
+// waves are added 0 + 1 + 2 + 3 and stored to part[matrix][slab][N]
+__global__ __launch_bounds__(256) void colsum_rows_kernel(ColsumRows set, int64_t ldx, int M, int N, int rows_per_block, float* __restrict__ part, int slabs) {
+    __shared__ float sm[4][64];
+    const float* __restrict__ X = set.x[blockIdx.z];
+    const float* __restrict__ wt = set.w[blockIdx.z];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int col = blockIdx.x * 64 + lane;
+    const int r0 = blockIdx.y * rows_per_block, r1 = min(M, r0 + rows_per_block);
+    float acc = 0.f;
+    if (col < N) {
+        int r = r0 + w;
+        for (; r + 12 < r1; r += 16) {
+            float v[4], s[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { v[u] = X[(int64_t)(r + 4 * u) * ldx + col]; s[u] = wt ? wt[r + 4 * u] : 1.f; }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc += s[u] * v[u];
+        }
+        for (; r < r1; r += 4) acc += (wt ? wt[r] : 1.f) * X[(int64_t)r * ldx + col];
+    }
+    sm[w][lane] = acc;
+    __syncthreads();
+    if (w == 0 && col < N) part[((int64_t)blockIdx.z * slabs + blockIdx.y) * N + col] = sm[0][lane] + sm[1][lane] + sm[2][lane] + sm[3][lane];
+}
+__global__ __launch_bounds__(256) void colsum_rows_finish_kernel(const float* __restrict__ part, int slabs, int N, ColsumRows set, int accumulate) {
+    colsum_finish_body(part + (size_t)blockIdx.y * slabs * N, slabs, N, set.out[blockIdx.y], accumulate);
+}
+}  // namespace
+
+SUBGC_API int subgc_colsum_rows_workspace_bytes(int M, int N, int n_mat, size_t* bytes) {
+    SUBGC_REQUIRE(M >= 0 && N >= 0 && (n_mat == 1 || n_mat == 2) && bytes, "colsum_rows_workspace_bytes: bad arguments");
+    const int rpb = colsum_rows_rpb(M, N), slabs = std::max(1, (M + rpb - 1) / rpb);
+    *bytes = (size_t)n_mat * slabs * N * sizeof(float);
+    return SUBGC_OK;
+}
+
+SUBGC_API int subgc_colsum_rows_f32(int n_mat, const float* X0, const float* X1, int64_t ldx, int M, int N, const float* w0, const float* w1,
+                                    float* out0, float* out1, int accumulate, void* workspace, size_t ws_bytes, void* stream) {
+    SUBGC_REQUIRE((n_mat == 1 || n_mat == 2) && M >= 0 && N >= 0 && ldx >= N, "colsum_rows: bad sizes");
+    if (N == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(out0 && (n_mat == 1 || out1) && (M == 0 || (X0 && (n_mat == 1 || X1))), "colsum_rows: null pointer");
+    const int rpb = colsum_rows_rpb(M, N), slabs = std::max(1, (M + rpb - 1) / rpb);
+    const size_t need = (size_t)n_mat * slabs * N * sizeof(float);
+    SUBGC_REQUIRE(workspace && ws_bytes >= need && (reinterpret_cast<uintptr_t>(workspace) & 3) == 0, "colsum_rows: needs %zu bytes of workspace (got %zu)",
+                  need, workspace ? ws_bytes : (size_t)0);
+    hipStream_t s = (hipStream_t)stream;
+    ColsumRows set{{X0, X1}, {w0, w1}, {out0, out1}};
+    float* part = static_cast<float*>(workspace);
+    hipLaunchKernelGGL(colsum_rows_kernel, dim3((N + 63) / 64, slabs, n_mat), dim3(256), 0, s, set, ldx, M, N, rpb, part, slabs);      // M == 0: one slab of zeros
+    hipLaunchKernelGGL(colsum_rows_finish_kernel, dim3((N + 63) / 64, n_mat), dim3(256), 0, s, (const float*)part, slabs, N, set, accumulate);
+    return subgc::check_launch("subgc_colsum_rows_f32");
 }

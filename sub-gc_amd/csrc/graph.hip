@@ -890,3 +890,154 @@ SUBGC_API int subgc_bn_bwd(const float* dY, const float* X, const float* gamma, 
                        (const float*)dgamma, (const float*)dbeta);
     return subgc::check_launch("subgc_bn_bwd");
 }
+
+// ------------------------------------------------------------------ aggregate first (include/subgc_gcn_agg_hip.h)
+// Collection units without BatchNorm are linear in front of their ReLU, so the 0/1 map is applied to the SOURCE rows and the two Linear
+// layers run on the (fewer) target rows.  gcn_agg_fwd_kernel is the gather of gcn_nodes_fwd_vec_kernel (CSR lists in LDS, float4 rows, four
+// rows of each role requested at a time) without its ReLU / role-average / residual epilogue: both roles read the SAME source X.
+#include "../../include/subgc_gcn_agg_hip.h"
+
+namespace {
+
+__global__ __launch_bounds__(256) void gcn_agg_fwd_kernel(const float* __restrict__ X, const int32_t* __restrict__ ptr,
+                                                          const int32_t* __restrict__ edges, float* __restrict__ A0, float* __restrict__ A1,
+                                                          float* __restrict__ s0, float* __restrict__ s1, int B, int N, int K, int L) {
+    extern __shared__ int sm_i[];
+    int* ps = sm_i; int* po = ps + (N + 1); int* es = po + (N + 1); int* eo = es + K;
+    const int b = blockIdx.y;
+    for (int i = threadIdx.x; i <= N; i += blockDim.x) {
+        ps[i] = ptr[((int64_t)0 * B + b) * (N + 1) + i];
+        po[i] = ptr[((int64_t)1 * B + b) * (N + 1) + i];
+    }
+    for (int i = threadIdx.x; i < K; i += blockDim.x) {
+        es[i] = edges[((int64_t)0 * B + b) * K + i];
+        eo[i] = edges[((int64_t)1 * B + b) * K + i];
+    }
+    __syncthreads();
+    const int col = (blockIdx.x * 256 + threadIdx.x) * 4;
+    const float* x = X + (int64_t)b * K * L + col;
+    for (int n = blockIdx.z; n < N; n += gridDim.z) {
+        const int c0 = ps[n + 1] - ps[n], c1 = po[n + 1] - po[n];
+        const float d0 = (float)c0 + 1e-7f, d1 = (float)c1 + 1e-7f;
+        if (blockIdx.x == 0 && threadIdx.x == 0) {                        // the bias scale of the row: rowsum(A) under the same normalisation
+            s0[(int64_t)b * N + n] = 0.5f * (float)c0 / d0;
+            s1[(int64_t)b * N + n] = 0.5f * (float)c1 / d1;
+        }
+        if (col >= L) continue;
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), c = a;
+        auto row = [&](int e) { return *reinterpret_cast<const float4*>(x + (int64_t)e * L); };
+        gather_pair(es, ps[n], ps[n + 1], row, eo, po[n], po[n + 1], row, a, c);
+        const int64_t o = ((int64_t)b * N + n) * L + col;
+        *reinterpret_cast<float4*>(A0 + o) = make_float4(a.x / d0 * 0.5f, a.y / d0 * 0.5f, a.z / d0 * 0.5f, a.w / d0 * 0.5f);
+        *reinterpret_cast<float4*>(A1 + o) = make_float4(c.x / d1 * 0.5f, c.y / d1 * 0.5f, c.z / d1 * 0.5f, c.w / d1 * 0.5f);
+    }
+}
+
+// dX[b,k,:] (+)= w0[s_k] dA0[b,s_k,:] + w1[o_k] dA1[b,o_k,:]: one subject and one object per relation -- a gather, no atomics
+__global__ __launch_bounds__(256) void gcn_agg_bwd_kernel(const float* __restrict__ dA0, const float* __restrict__ dA1,
+                                                          const int64_t* __restrict__ rel_ind, const int32_t* __restrict__ ptr,
+                                                          float* __restrict__ dX, int accumulate, int B, int N, int K, int L) {
+    extern __shared__ int sm_i[];
+    int* ns = sm_i; int* no = ns + K;
+    float* w0 = reinterpret_cast<float*>(no + K); float* w1 = w0 + N;
+    const int b = blockIdx.y;
+    for (int k = threadIdx.x; k < K; k += blockDim.x) {
+        int64_t s = rel_ind[((int64_t)b * K + k) * 2 + 0], o = rel_ind[((int64_t)b * K + k) * 2 + 1];
+        ns[k] = (int)(s < 0 ? 0 : (s >= N ? N - 1 : s));
+        no[k] = (int)(o < 0 ? 0 : (o >= N ? N - 1 : o));
+    }
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {
+        const int32_t* p0 = ptr + ((int64_t)0 * B + b) * (N + 1);
+        const int32_t* p1 = ptr + ((int64_t)1 * B + b) * (N + 1);
+        w0[n] = 0.5f / ((float)(p0[n + 1] - p0[n]) + 1e-7f);
+        w1[n] = 0.5f / ((float)(p1[n + 1] - p1[n]) + 1e-7f);
+    }
+    __syncthreads();
+    const int col = (blockIdx.x * 256 + threadIdx.x) * 4;
+    if (col >= L) return;
+    const int kz = gridDim.z;
+    for (int k0 = blockIdx.z; k0 < K; k0 += 4 * kz) {                      // four relations' target rows requested before the first is used
+        float4 xs[4], xo[4], old[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = k0 + u * kz;
+            if (k < K) {
+                xs[u] = *reinterpret_cast<const float4*>(dA0 + ((int64_t)b * N + ns[k]) * L + col);
+                xo[u] = *reinterpret_cast<const float4*>(dA1 + ((int64_t)b * N + no[k]) * L + col);
+                if (accumulate) old[u] = *reinterpret_cast<const float4*>(dX + ((int64_t)b * K + k) * L + col);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int k = k0 + u * kz;
+            if (k < K) {
+                const float a = w0[ns[k]], c = w1[no[k]];
+                float4 v = make_float4(a * xs[u].x + c * xo[u].x, a * xs[u].y + c * xo[u].y, a * xs[u].z + c * xo[u].z, a * xs[u].w + c * xo[u].w);
+                if (accumulate) { v.x += old[u].x; v.y += old[u].y; v.z += old[u].z; v.w += old[u].w; }
+                *reinterpret_cast<float4*>(dX + ((int64_t)b * K + k) * L + col) = v;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void gcn_agg_relu_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ y0, const float* __restrict__ y1,
+                                                               float* __restrict__ dz0, float* __restrict__ dz1, int64_t n, int vec) {
+    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+    if (vec) {
+        for (int64_t i = i0; i < n / 4; i += step) {
+            const float4 g = reinterpret_cast<const float4*>(dy)[i], a = reinterpret_cast<const float4*>(y0)[i], c = reinterpret_cast<const float4*>(y1)[i];
+            reinterpret_cast<float4*>(dz0)[i] = make_float4(a.x > 0.f ? g.x : 0.f, a.y > 0.f ? g.y : 0.f, a.z > 0.f ? g.z : 0.f, a.w > 0.f ? g.w : 0.f);
+            reinterpret_cast<float4*>(dz1)[i] = make_float4(c.x > 0.f ? g.x : 0.f, c.y > 0.f ? g.y : 0.f, c.z > 0.f ? g.z : 0.f, c.w > 0.f ? g.w : 0.f);
+        }
+        return;
+    }
+    for (int64_t i = i0; i < n; i += step) {
+        dz0[i] = y0[i] > 0.f ? dy[i] : 0.f;
+        dz1[i] = y1[i] > 0.f ? dy[i] : 0.f;
+    }
+}
+
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+}  // namespace
+
+SUBGC_API int subgc_gcn_agg_fwd(const float* X, const int32_t* ptr, const int32_t* edges, float* Xagg0, float* Xagg1, float* s0, float* s1,
+                                int B, int N, int K, int L, void* stream) {
+    SUBGC_REQUIRE(B >= 0 && N > 0 && K > 0 && L > 0 && L % 4 == 0, "gcn_agg_fwd: bad sizes (L must be a multiple of 4)");
+    if (B == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(X && ptr && edges && Xagg0 && Xagg1 && s0 && s1, "gcn_agg_fwd: null pointer");
+    SUBGC_REQUIRE(al16(X) && al16(Xagg0) && al16(Xagg1), "gcn_agg_fwd: rows must be 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    subgc::ProfScope prof(SUBGC_FAM_GCN, s, 4.0 * B * L * (2.0 * K + 2.0 * N));
+    const size_t lds = sizeof(int) * (2 * (N + 1) + 2 * K);
+    const int cg = (L / 4 + 255) / 256;
+    hipLaunchKernelGGL(gcn_agg_fwd_kernel, dim3(cg, B, subgc::gcn_zsplit(cg, B, N)), dim3(256), lds, s, X, ptr, edges, Xagg0, Xagg1, s0, s1, B, N, K, L);
+    return subgc::check_launch("subgc_gcn_agg_fwd");
+}
+
+SUBGC_API int subgc_gcn_agg_bwd(const float* dXagg0, const float* dXagg1, const int64_t* rel_ind, const int32_t* ptr, float* dX, int accumulate,
+                                int B, int N, int K, int L, void* stream) {
+    SUBGC_REQUIRE(B >= 0 && N > 0 && K > 0 && L > 0 && L % 4 == 0, "gcn_agg_bwd: bad sizes (L must be a multiple of 4)");
+    if (B == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(dXagg0 && dXagg1 && rel_ind && ptr && dX, "gcn_agg_bwd: null pointer");
+    SUBGC_REQUIRE(al16(dXagg0) && al16(dXagg1) && al16(dX), "gcn_agg_bwd: rows must be 16-byte aligned");
+    SUBGC_DEBUG_RANGE(rel_ind, 8, (int64_t)B * K, 2, 2, 0, N - 1, -1, "gcn_agg_bwd: rel_ind", stream);
+    hipStream_t s = (hipStream_t)stream;
+    subgc::ProfScope prof(SUBGC_FAM_GCN, s, 4.0 * B * L * (2.0 * K + (accumulate ? 2.0 : 1.0) * K));
+    const size_t lds = sizeof(int) * (2 * K) + sizeof(float) * 2 * N;
+    const int cg = (L / 4 + 255) / 256;
+    hipLaunchKernelGGL(gcn_agg_bwd_kernel, dim3(cg, B, subgc::gcn_zsplit(cg, B, (K + 3) / 4)), dim3(256), lds, s, dXagg0, dXagg1, rel_ind, ptr, dX,
+                       accumulate ? 1 : 0, B, N, K, L);
+    return subgc::check_launch("subgc_gcn_agg_bwd");
+}
+
+SUBGC_API int subgc_gcn_agg_relu_bwd(const float* dy, const float* y0, const float* y1, float* dz0, float* dz1, int64_t n, void* stream) {
+    SUBGC_REQUIRE(n >= 0, "gcn_agg_relu_bwd: bad size");
+    if (n == 0) return SUBGC_OK;
+    SUBGC_REQUIRE(dy && y0 && y1 && dz0 && dz1, "gcn_agg_relu_bwd: null pointer");
+    const int vec = n % 4 == 0 && al16(dy) && al16(y0) && al16(y1) && al16(dz0) && al16(dz1);
+    const int64_t items = vec ? n / 4 : n;
+    hipLaunchKernelGGL(gcn_agg_relu_bwd_kernel, dim3((unsigned)std::min<int64_t>((items + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, dy, y0, y1,
+                       dz0, dz1, n, vec);
+    return subgc::check_launch("subgc_gcn_agg_relu_bwd");
+}

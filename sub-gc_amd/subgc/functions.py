@@ -371,6 +371,86 @@ class GcnNodesFn(Function):
         return dF0, dF1, (dX if ctx.has_skip else None), None, None, None, None
 
 
+class GcnAggFirstFn(Function):
+    """nodes <- relations for a layer WITHOUT BatchNorm, aggregation first (ops.GCN_AGGREGATE_FIRST; units 0,1 of graph_conv.py:24-26 and
+    the residual, graph_conv_unit.py:28-36 with gcn_bn = 0).  Everything in front of a unit's ReLU is linear, and the targets (B * N node
+    rows) are fewer than the sources (B * K relation rows), so the 0/1 map is applied to the source rows and the Linear layers run on
+    B * N rows per role:
+
+      forward   Xagg_r = S_r A_r x,  s_r = S_r cnt_r           S_r = diag(0.5 / (cnt_r + 1e-7))      subgc_gcn_agg_fwd
+                H_r = Xagg_r Wl_r^T + s_r bl_r^T                both roles: ONE pair launch, per-row bias scale
+                Y_r = relu(H_r Wr_r^T + s_r br_r^T)             likewise, ReLU in the epilogue
+                out = Y_0 + Y_1 [+ skip]                        the 0.5 of the role average sits in S_r (it commutes with the ReLU)
+      backward  dY_r = [Y_r > 0] d(out);  dH_r = dY_r Wr_r;  dXagg_r = dH_r Wl_r          one mask launch, two pair launches
+                dWr_r += dY_r^T H_r,  dbr_r += s_r^T dY_r,  dWl_r += dH_r^T Xagg_r,  dbl_r += s_r^T dH_r
+                dx[k] = w_0[subj k] dXagg_0[subj k] + w_1[obj k] dXagg_1[obj k]          a gather: no atomics
+
+    (A x) W^T against the unit-by-unit A (x W^T): the same mathematical result, fp32 sums in another order.  x [B*K, L] fp32."""
+
+    @staticmethod
+    def forward(ctx, x, skip, rel_ind, ptr, edges, B, N, K, Wl_a, bl_a, Wl_b, bl_b, Wr_a, br_a, Wr_b, br_b):
+        dev, L, Lr = x.device, x.size(1), Wl_a.size(0)
+        x = x.contiguous()
+        A0, A1, s0, s1 = ops.gcn_agg_fwd(x, ptr, edges, B, N, K, L)
+        M = B * N
+        H0, H1 = (torch.empty(M, Lr, device=dev, dtype=torch.float32) for _ in range(2))
+        ops.gemm_pair_rowbias(A0, A1, Wl_a, Wl_b, H0, H1, tb=True, bias1=bl_a, bias2=bl_b, scale1=s0, scale2=s1)
+        Y0, Y1 = (torch.empty(M, Wr_a.size(0), device=dev, dtype=torch.float32) for _ in range(2))
+        ops.gemm_pair_rowbias(H0, H1, Wr_a, Wr_b, Y0, Y1, tb=True, bias1=br_a, bias2=br_b, scale1=s0, scale2=s1, relu=True)
+        out = ops.add_n([Y0, Y1] + ([skip.reshape(M, -1)] if skip is not None else []))
+        ctx.save_for_backward(A0, A1, s0, s1, H0, H1, Y0, Y1, rel_ind, ptr, Wl_a, Wl_b, Wr_a, Wr_b)
+        ctx.params = (Wl_a, bl_a, Wl_b, bl_b, Wr_a, br_a, Wr_b, br_b)
+        ctx.dims, ctx.has_skip = (B, N, K, L), skip is not None
+        return out.view(B, N, -1)
+
+    @staticmethod
+    def backward(ctx, dout):
+        A0, A1, s0, s1, H0, H1, Y0, Y1, rel_ind, ptr, Wl_a, Wl_b, Wr_a, Wr_b = ctx.saved_tensors
+        B, N, K, L = ctx.dims
+        dev, M, Lr = dout.device, B * N, H0.size(1)
+        dout = dout.contiguous()
+        dY0, dY1 = ops.gcn_agg_relu_bwd(dout.view(M, -1), Y0, Y1)
+        dH0, dH1 = (torch.empty(M, Lr, device=dev, dtype=torch.float32) for _ in range(2))
+        ops.gemm_pair(dY0, dY1, Wr_a, Wr_b, dH0, dH1)
+        ret = [None] * 8
+        pw = ctx.params
+        # weight gradients over the B * N target rows, straight into the flat bucket where it exists
+        for i, (dz, xin) in ((0, (dH0, A0)), (2, (dH1, A1)), (4, (dY0, H0)), (6, (dY1, H1))):
+            g = _direct(pw[i], dev)
+            if g is not None:
+                ops.gemm(dz, xin, g, ta=True, accum=True)
+            else:
+                ret[i] = torch.empty(pw[i].shape, device=dev, dtype=torch.float32)
+                ops.gemm(dz, xin, ret[i], ta=True)
+        # bias gradients: the rows weighted by their bias scale, the two roles of one width in one launch
+        for ia, ib, za, zb in ((1, 3, dH0, dH1), (5, 7, dY0, dY1)):
+            ga, gb = _direct(pw[ia], dev), _direct(pw[ib], dev)
+            if (ga is None) == (gb is None):
+                if ga is None:
+                    ga, gb = (torch.empty(z.size(1), device=dev, dtype=torch.float32) for z in (za, zb))
+                    ret[ia], ret[ib] = ga, gb
+                    ops.colsum_rows((za, zb), (s0, s1), (ga, gb), accumulate=False)
+                else:
+                    ops.colsum_rows((za, zb), (s0, s1), (ga, gb), accumulate=True)
+            else:
+                for j, g, z, s in ((ia, ga, za, s0), (ib, gb, zb, s1)):
+                    if g is None:
+                        ret[j] = torch.empty(z.size(1), device=dev, dtype=torch.float32)
+                    ops.colsum_rows((z,), (s,), (g if g is not None else ret[j],), accumulate=g is not None)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dA0, dA1 = (torch.empty(M, L, device=dev, dtype=torch.float32) for _ in range(2))
+            ops.gemm_pair(dH0, dH1, Wl_a, Wl_b, dA0, dA1)
+            dx = ops.gcn_agg_bwd(dA0, dA1, rel_ind, ptr, B, N, K, L)
+        return (dx, (dout if ctx.has_skip else None), None, None, None, None, None, None) + tuple(ret)
+
+
+def gcn_aggregate_first_ok(gcn_bn, bf16, B, N, K, L):
+    """The host-side choice of the aggregation-first order (ops.GCN_AGGREGATE_FIRST): no BatchNorm in front of the aggregation, fp32 storage,
+    fewer target (node) rows than source (relation) rows, float4-legal rows."""
+    return bool(ops.GCN_AGGREGATE_FIRST) and not gcn_bn and not bf16 and N < K and L % 4 == 0
+
+
 class GcnNodesB16Fn(Function):
     """GcnNodesFn for bf16-STORED unit outputs (compute_dtype = bf16, no BatchNorm: Sub-GC presets): the normalise-on-load kernels with the
     identity triple read the bf16 GEMM results as they are, d(y) leaves the backward in bf16 (what the Linear backward's GEMMs consume),

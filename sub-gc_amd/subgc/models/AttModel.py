@@ -559,7 +559,13 @@ class AttModel(CaptionModel):
             raw16 = w16 is not None and not self.GCN_use_bn and L % 8 == 0                  # bf16 storage, no BatchNorm: unit outputs stay bf16
             nxt_x = w16 is not None and l + 1 < self.GCN_layers and live_edges[l + 1]          # the next layer reads new_x as a GEMM operand
             nxt_p = w16 is not None and l + 1 < self.GCN_layers and live_nodes[l + 1]
-            if live_nodes[l]:
+            if live_nodes[l] and F_.gcn_aggregate_first_ok(self.GCN_use_bn, w16 is not None, B, N, K, L):
+                # no BatchNorm and fewer node rows than relation rows: aggregate the source rows, then fc_lft / fc_rgt on B * N rows per
+                # role (functions.GcnAggFirstFn) -- the paired and the unit-by-unit configuration share this order
+                pu = [self.P(f"gcn_backbone.gcn.{l}.gcn_collect.collect_units.{u}.{fc}.{wb}")
+                      for fc in ("fc_lft", "fc_rgt") for u in (0, 1) for wb in ("weight", "bias")]
+                new_x = F_.GcnAggFirstFn.apply(ps[0].reshape(B * K, L), skip_x if res else None, rel_ind, ptr, edges, B, N, K, *pu)
+            elif live_nodes[l]:
                 y0, y1 = self._unit_pair(l, 0, ps[0], p16, flat16, fuse, raw16)
                 if fuse:
                     r = F_.GcnNodesBnFn.apply(y0, y1, skip_x if res else None, rel_ind, ptr, edges, N, *self._bn_args(l, 0, 1), nxt_x)

@@ -11,7 +11,7 @@ import math
 
 import torch
 
-from ._lib import SubgcError, call, call_beam_att, call_consensus, call_criterion, call_decode_b16, call_selfcritical, lib
+from ._lib import SubgcError, call, call_beam_att, call_consensus, call_criterion, call_decode_b16, call_gcn_agg, call_selfcritical, lib
 from . import _scoring
 
 RELU, ACCUM = 1, 2
@@ -511,6 +511,93 @@ def gcn_nodes_bwd(dX, act, rel_ind, ptr, B, N, K, L, bf16=False):
     dF1 = torch.empty_like(dF0)
     call("subgc_gcn_nodes_bwd", _ptr(dX), _ptr(act), _ptr(rel_ind), _ptr(ptr), _ptr(dF0), _ptr(dF1), int(bf16), B, N, K, L, _stream())
     return dF0, dF1
+
+
+# Collection units WITHOUT BatchNorm whose targets are fewer than their sources (nodes <- relations: 37 against 65 rows per image) apply the
+# 0/1 map to the 1024-wide source rows first and run fc_lft / fc_rgt per role on the target rows (functions.GcnAggFirstFn):
+# (A X) W^T in place of A (X W^T).  False: the launches of the paired units + gcn_nodes_fwd, exactly as before.
+GCN_AGGREGATE_FIRST = True
+
+
+def gcn_agg_fwd(X, ptr, edges, B, N, K, L):
+    """-> (Xagg0, Xagg1 [B*N, L], s0, s1 [B*N]): per role 0.5 * (sum of the node's relation rows) / (cnt + 1e-7) and the bias scale
+    0.5 * cnt / (cnt + 1e-7) of the row (subgc_gcn_agg_fwd)."""
+    A0, A1 = (torch.empty(B * N, L, device=X.device, dtype=torch.float32) for _ in range(2))
+    s0, s1 = (torch.empty(B * N, device=X.device, dtype=torch.float32) for _ in range(2))
+    call_gcn_agg("subgc_gcn_agg_fwd", _ptr(X, torch.float32), _ptr(ptr, torch.int32), _ptr(edges, torch.int32), _ptr(A0), _ptr(A1), _ptr(s0), _ptr(s1),
+                 B, N, K, L, _stream())
+    return A0, A1, s0, s1
+
+
+def gcn_agg_bwd(dA0, dA1, rel_ind, ptr, B, N, K, L, out=None):
+    """d(source) [B*K, L] of gcn_agg_fwd: a gather of one subject and one object row per relation; `out` given: added to it."""
+    dX = out if out is not None else torch.empty(B * K, L, device=dA0.device, dtype=torch.float32)
+    call_gcn_agg("subgc_gcn_agg_bwd", _ptr(dA0, torch.float32), _ptr(dA1, torch.float32), _ptr(rel_ind, torch.int64), _ptr(ptr, torch.int32),
+                 _ptr(dX, torch.float32), int(out is not None), B, N, K, L, _stream())
+    return dX
+
+
+def gcn_agg_relu_bwd(dy, y0, y1):
+    """-> (dy where y0 > 0, dy where y1 > 0): the ReLU masks of the two roles from the stored outputs, one launch."""
+    dz0, dz1 = torch.empty_like(y0), torch.empty_like(y1)
+    call_gcn_agg("subgc_gcn_agg_relu_bwd", _ptr(dy, torch.float32), _ptr(y0, torch.float32), _ptr(y1, torch.float32), _ptr(dz0), _ptr(dz1), dy.numel(), _stream())
+    return dz0, dz1
+
+
+def gemm_rowbias(a, b, out, *, ta=False, tb=False, bias=None, bias_scale=None, relu=False, accum=False):
+    """`gemm` on fp32 operands with the bias of row m entering as bias_scale[m] * bias (subgc_gemm_f32_rowbias; bias_scale None = the
+    plain bias): A (X W^T + 1 b^T) = (A X) W^T + rowsum(A) b^T."""
+    M = a.size(1) if ta else a.size(0)
+    K = a.size(0) if ta else a.size(1)
+    N = b.size(0) if tb else b.size(1)
+    if K != (b.size(1) if tb else b.size(0)) or out.size(0) < M or out.size(1) != N or (bias_scale is not None and bias_scale.numel() != M):
+        raise SubgcError(f"gemm_rowbias shape mismatch: op(a)=[{M},{K}] op(b)=[..,{N}] out={tuple(out.shape)}")
+    if FLOPS["on"]:
+        FLOPS["gemm"] += 2.0 * M * N * K
+        FLOPS["gemm_bytes"] += 4.0 * (M * K + K * N + M * N * (2 if accum else 1))
+        FLOPS["gemm_calls"] += 1
+    call_gcn_agg("subgc_gemm_f32_rowbias", int(ta), int(tb), M, N, K, _ptr(a, torch.float32), ld(a), _ptr(b, torch.float32), ld(b),
+                 _ptr(out, torch.float32), ld(out), _ptr(bias, torch.float32), _ptr(bias_scale, torch.float32),
+                 (RELU if relu else 0) | (ACCUM if accum else 0) | GEMM_MODES[gemm_mode.current] | gemm_tune.f32_bits, *_ws(a), _stream())
+    return out
+
+
+def gemm_pair_rowbias(a1, a2, b1, b2, out1, out2, *, tb=False, bias1=None, bias2=None, scale1=None, scale2=None, relu=False):
+    """`gemm_pair` on fp32 operands with per-row bias scales and an optional ReLU (subgc_gemm_f32_pair_rowbias); operands that do not form
+    a pair (or PAIR_LAUNCHES off) run as two `gemm_rowbias` calls."""
+    same = (PAIR_LAUNCHES and a1.shape == a2.shape and b1.shape == b2.shape and out1.shape == out2.shape and ld(a1) == ld(a2) and ld(b1) == ld(b2)
+            and ld(out1) == ld(out2) and (bias1 is None) == (bias2 is None) and (scale1 is None) == (scale2 is None))
+    if not same:
+        gemm_rowbias(a1, b1, out1, tb=tb, bias=bias1, bias_scale=scale1, relu=relu)
+        gemm_rowbias(a2, b2, out2, tb=tb, bias=bias2, bias_scale=scale2, relu=relu)
+        return out1, out2
+    M, K = a1.shape
+    N = b1.size(0) if tb else b1.size(1)
+    if K != (b1.size(1) if tb else b1.size(0)) or out1.size(0) < M or out1.size(1) != N or (scale1 is not None and scale1.numel() != M):
+        raise SubgcError(f"gemm_pair_rowbias shape mismatch: a=[{M},{K}] op(b)=[..,{N}] out={tuple(out1.shape)}")
+    if FLOPS["on"]:
+        FLOPS["gemm"] += 4.0 * M * N * K
+        FLOPS["gemm_bytes"] += 2.0 * 4.0 * (M * K + K * N + M * N)
+        FLOPS["gemm_calls"] += 1
+    call_gcn_agg("subgc_gemm_f32_pair_rowbias", 0, int(tb), M, N, K, _ptr(a1, torch.float32), _ptr(a2, torch.float32), ld(a1), _ptr(b1, torch.float32),
+                 _ptr(b2, torch.float32), ld(b1), _ptr(out1, torch.float32), _ptr(out2, torch.float32), ld(out1), _ptr(bias1, torch.float32),
+                 _ptr(bias2, torch.float32), _ptr(scale1, torch.float32), _ptr(scale2, torch.float32),
+                 (RELU if relu else 0) | GEMM_MODES[gemm_mode.current] | gemm_tune.f32_bits, *_ws(a1), _stream())
+    return out1, out2
+
+
+def colsum_rows(xs, ws, outs, accumulate=False):
+    """outs[q][c] (+)= sum_i ws[q][i] * xs[q][i, c] for one or two fp32 matrices of one shape and leading dimension (subgc_colsum_rows_f32:
+    slabs of rows, added in slab order -- no atomics).  The slab partials live in the registered GEMM workspace."""
+    x0 = xs[0]
+    M, N = x0.shape
+    n = len(xs)
+    if n not in (1, 2) or any(x.shape != x0.shape or ld(x) != ld(x0) for x in xs) or any(w.numel() != M for w in ws) or any(o.numel() != N for o in outs):
+        raise SubgcError("colsum_rows: one or two matrices of one shape, one weight per row, one output per column")
+    px = [_ptr(x, torch.float32) for x in xs] + [None] * (2 - n)
+    pw = [_ptr(w, torch.float32) for w in ws] + [None] * (2 - n)
+    po = [_ptr(o, torch.float32) for o in outs] + [None] * (2 - n)
+    call_gcn_agg("subgc_colsum_rows_f32", n, px[0], px[1], ld(x0), M, N, pw[0], pw[1], po[0], po[1], int(accumulate), *_ws(x0), _stream())
 
 
 def gcn_edges_fwd(F2, F3, rel_ind, skip, B, N, K, L):
