@@ -28,6 +28,8 @@ HEADERS = {"core": "subgc_hip.h", "metrics": "subgc_metrics_hip.h", "grounding":
 EXTRA_HEADERS = {"decode_b16": "subgc_decode_b16_hip.h"}
 # ... and headers added after that table was pinned in its turn: the same again.
 LATER_HEADERS = {"gcn_agg": "subgc_gcn_agg_hip.h"}
+# ... and after that one was pinned too.
+NEWER_HEADERS = {"neighbours": "subgc_neighbours_hip.h"}
 HEADER = os.path.join(_INCLUDE, HEADERS["core"])
 METRICS_HEADER = os.path.join(_INCLUDE, HEADERS["metrics"])
 GROUNDING_HEADER = os.path.join(_INCLUDE, HEADERS["grounding"])
@@ -40,6 +42,7 @@ CONTROL_INPUT_HEADER = os.path.join(_INCLUDE, HEADERS["control_input"])
 BEAM_ATT_HEADER = os.path.join(_INCLUDE, HEADERS["beam_att"])
 DECODE_B16_HEADER = os.path.join(_INCLUDE, EXTRA_HEADERS["decode_b16"])
 GCN_AGG_HEADER = os.path.join(_INCLUDE, LATER_HEADERS["gcn_agg"])
+NEIGHBOURS_HEADER = os.path.join(_INCLUDE, NEWER_HEADERS["neighbours"])
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -96,7 +99,7 @@ def parse_struct(name, path=HEADER):
 
 
 _lib = None
-PROTOS = {}         # key of HEADERS / EXTRA_HEADERS / LATER_HEADERS -> its parsed prototypes; filled once by lib()
+PROTOS = {}         # key of HEADERS / EXTRA_HEADERS / LATER_HEADERS / NEWER_HEADERS -> its parsed prototypes; filled once by lib()
 _protos = None      # PROTOS["core"]: what `call` checks
 
 
@@ -107,7 +110,7 @@ def lib():
             raise SubgcError(f"{LIB_PATH} is missing: run `python sub-gc_amd/build.py` (hipcc, gfx950). "
                              "There is no CPU fallback for the Sub-GC hot path.")
         L = ctypes.CDLL(LIB_PATH)
-        for key, hdr in {**HEADERS, **EXTRA_HEADERS, **LATER_HEADERS}.items():
+        for key, hdr in {**HEADERS, **EXTRA_HEADERS, **LATER_HEADERS, **NEWER_HEADERS}.items():
             PROTOS[key] = parse_header(os.path.join(_INCLUDE, hdr))
             for name, (ret, args) in PROTOS[key].items():
                 try:
@@ -140,9 +143,9 @@ def call(name, *args):
 
 
 def _invoker(key):
-    """`call` for the entry points of one header of HEADERS / EXTRA_HEADERS: a cache of its own, so that no invoker reaches another's
+    """`call` for the entry points of one header of HEADERS / EXTRA_HEADERS / LATER_HEADERS / NEWER_HEADERS: a cache of its own, so that no invoker reaches another's
     declarations."""
-    cache, hdr = {}, {**HEADERS, **EXTRA_HEADERS, **LATER_HEADERS}[key]
+    cache, hdr = {}, {**HEADERS, **EXTRA_HEADERS, **LATER_HEADERS, **NEWER_HEADERS}[key]
 
     def invoke(name, *args):
         fn = cache.get(name)
@@ -169,6 +172,7 @@ call_control_input = _invoker("control_input")
 call_beam_att = _invoker("beam_att")
 call_decode_b16 = _invoker("decode_b16")
 call_gcn_agg = _invoker("gcn_agg")
+call_neighbours = _invoker("neighbours")
 
 FAM = {"gemm": 1, "attn": 2, "lstm": 3, "gcn": 4, "pool": 5, "softmax": 6}
 

@@ -14,8 +14,10 @@ class and the reference's defaults (conf_cr.py:43-48) by method name.
 Tie rule: `np.argsort(-sim)` leaves the order of equal sums unspecified, and duplicate captions from different sub-graphs make exact
 ties routine.  The device order is STABLE: among equal sums the lower candidate index comes first.
 
-Out of scope: the nearest-image search (`find_NNimg`, a float64 cdist over ResNet features that are not shipped) -- the caller supplies
-the neighbour index lists the reference caches as `NNimg_list_*.npy`; PTB tokenisation and the COCO metric scripts.
+The neighbour lists are either the host lists the reference caches as `NNimg_list_*.npy` or a device int32 tensor -- the output of
+`neighbours.ImageIndex.search` (`find_NNimg` on the device), which `caption_images(consensus={"index": ...})` runs in the same pass.
+
+Out of scope: extracting the ResNet features the search runs over; PTB tokenisation and the COCO metric scripts.
 """
 from __future__ import annotations
 
@@ -25,6 +27,7 @@ import torch
 from . import ops
 from ._lib import SubgcError
 from ._scoring import MAX_IDS, bad_table, resolve_device
+from .neighbours import WORKSPACE_BYTES
 
 MAX_WORDS = 256          # words of one corpus caption (subgc_consensus_cook)
 MAX_CAPS = 2048          # neighbour captions per image (subgc_consensus_score)
@@ -175,6 +178,28 @@ class ConsensusReranker:
         if not 1 <= k <= MAX_K:
             raise SubgcError(f"consensus: k = {k}; 1 <= k <= {MAX_K} neighbour images")
         self.corpus, self.k, self.m = corpus, int(k), int(m)
+        self._caps_bound = None
+
+    def caps_bound(self):
+        """The neighbour-caption capacity for lists that live on the device and cannot be read here: the sum of the k largest per-image
+        caption counts of the corpus, an upper bound for every list; computed once.  A capacity only: the kernels score the captions
+        that are there, so any value >= the true count gives the same bits."""
+        if self._caps_bound is None:
+            per_img = np.sort(np.diff(self.corpus.cap_off))
+            self._caps_bound = int(per_img[-self.k:].sum())
+        if self._caps_bound > MAX_CAPS:
+            raise SubgcError(f"consensus: the {self.k} largest images of the corpus hold {self._caps_bound} captions; the limit is {MAX_CAPS} "
+                             "neighbour captions per image, and lists on the device cannot be counted one by one")
+        return self._caps_bound
+
+    def device_neighbours(self, nn, I, device):
+        """A device int32 [I, >= k] tensor of neighbour indices with unit inner stride (ImageIndex.search's `idx`) -> (it, caps_bound())."""
+        if not nn.is_cuda or nn.device != device:
+            raise SubgcError("consensus: a neighbour tensor lives on the device of the token rows; host lists go in as lists")
+        if nn.dtype != torch.int32 or nn.dim() != 2 or nn.size(0) != I or nn.size(1) < self.k or (nn.size(1) > 1 and nn.stride(1) != 1):
+            raise SubgcError(f"consensus: a neighbour tensor is int32 [{I}, >= k = {self.k}] with unit inner stride, got {nn.dtype} "
+                             f"{tuple(nn.shape)} / {nn.stride()}")
+        return nn, self.caps_bound()
 
     def neighbours(self, nn_lists):
         """-> (int32 [I, k] array of the first k neighbours, the largest neighbour-caption count of an image); host work, numpy."""
@@ -192,7 +217,8 @@ class ConsensusReranker:
 
     def enqueue(self, seq, seg, I, max_rows, nn_lists, top_k, remove_bad_endings, sim, order, first=None, pair_out=None):
         """The three launches on the current stream.  seq: device token rows [rows, T] (int32 / int64) in candidate order; seg: device
-        int32 row boundaries (>= I + 1 entries); sim fp64 [rows], order int32 [rows], first int32 [I]: device outputs."""
+        int32 row boundaries (>= I + 1 entries); sim fp64 [rows], order int32 [rows], first int32 [I]: device outputs.  nn_lists: per image
+        a host list of neighbour indices, or ONE device int32 [I, >= k] tensor (`device_neighbours`), read where it lies."""
         c = self.corpus
         if c.device is None:
             raise SubgcError("consensus: the corpus is not on a device (ConsensusCorpus(..., device=...) or .to(device))")
@@ -202,8 +228,11 @@ class ConsensusReranker:
         top_k = 0 if top_k is None else int(top_k)
         if top_k < 0:
             raise SubgcError("consensus: top_k >= 1 or None")
-        nn, max_caps = self.neighbours(nn_lists)
-        d_nn = torch.from_numpy(nn).to(seq.device)
+        if torch.is_tensor(nn_lists):
+            d_nn, max_caps = self.device_neighbours(nn_lists, I, seq.device)
+        else:
+            nn, max_caps = self.neighbours(nn_lists)
+            d_nn = torch.from_numpy(nn).to(seq.device)
         self._score(seq, T, seg, I, max_rows, top_k, d_nn, max_caps, remove_bad_endings, sim, pair_out)
         ops.consensus_rank(sim, seg, I, top_k, order, first)
         return max_caps
@@ -220,14 +249,39 @@ class ConsensusReranker:
         `batch.c_first`, the device int32 [I] first choices, for the accuracy and grounding passes."""
         rows, I = batch.rows, batch.I
         w_sim, w_order, w_first = slots.words(2 * rows, align8=True), slots.words(rows), slots.words(I)
+        if ("nn" in arg) == ("index" in arg):
+            raise SubgcError("consensus: exactly one of 'nn' (host neighbour lists) and 'index' (an ImageIndex, with 'features') is needed")
+        if "nn" in arg:
+            def enqueue():
+                batch.c_first = slots.arena[w_first]
+                if I and rows:
+                    self.enqueue(batch.seq_s, batch.seg, I, batch.max_rows, arg["nn"], arg.get("top_k"), arg.get("remove_bad_endings", 0),
+                                 slots.arena[w_sim].view(torch.float64), slots.arena[w_order], batch.c_first)
+
+            return enqueue, lambda host: {"c_sim": host[w_sim].view(np.float64).copy(), "c_order": host[w_order].copy(), "c_first": host[w_first].copy()}
+        # the search in the same pass: the batch's query rows go up now, `search` writes its int32 lists straight into the batch's arena
+        # (so they ride in its one copy) and the score launch reads their first k columns there (nn_ld = k_search)
+        index = arg["index"]
+        k_search = index.check_k(arg.get("k_search", self.k))
+        if k_search < self.k:
+            raise SubgcError(f"consensus: k_search = {k_search} is smaller than the re-ranker's k = {self.k}")
+        if len(arg["features"]) != I:
+            raise SubgcError("consensus: one feature vector per image")
+        self.caps_bound()
+        w_nn = slots.words(I * k_search)
+        d_q = index.queries(np.stack([np.asarray(f).reshape(-1) for f in arg["features"]])) if I else None
 
         def enqueue():
             batch.c_first = slots.arena[w_first]
-            if I and rows:
-                self.enqueue(batch.seq_s, batch.seg, I, batch.max_rows, arg["nn"], arg.get("top_k"), arg.get("remove_bad_endings", 0),
-                             slots.arena[w_sim].view(torch.float64), slots.arena[w_order], batch.c_first)
+            if I:
+                d_nn = slots.arena[w_nn].view(I, k_search)
+                index.search(d_q, k_search, arg.get("workspace_bytes", WORKSPACE_BYTES), idx=d_nn, want_dist=False)
+                if rows:
+                    self.enqueue(batch.seq_s, batch.seg, I, batch.max_rows, d_nn, arg.get("top_k"), arg.get("remove_bad_endings", 0),
+                                 slots.arena[w_sim].view(torch.float64), slots.arena[w_order], batch.c_first)
 
-        return enqueue, lambda host: {"c_sim": host[w_sim].view(np.float64).copy(), "c_order": host[w_order].copy(), "c_first": host[w_first].copy()}
+        return enqueue, lambda host: {"c_sim": host[w_sim].view(np.float64).copy(), "c_order": host[w_order].copy(), "c_first": host[w_first].copy(),
+                                      "c_nn": host[w_nn].reshape(I, k_search)[:, :self.k].copy()}
 
     def rerank(self, seq, bounds, nn_lists, top_k=None, remove_bad_endings=0, return_pairs=False):
         """seq [rows, T]: the decode batch's device token rows, image i owning rows bounds[i] .. bounds[i+1]-1 in sGPN-ranked order;
@@ -249,7 +303,7 @@ class ConsensusReranker:
         sim, order = arena[:2 * rows].view(torch.float64), arena[2 * rows:]
         pairs = None
         if return_pairs:
-            _, mc = self.neighbours(nn_lists)
+            mc = self.caps_bound() if torch.is_tensor(nn_lists) else self.neighbours(nn_lists)[1]
             pairs = torch.empty(rows, max(mc, 1), device=dev, dtype=torch.float64)
         self.enqueue(seq.contiguous(), seg, I, max_rows, nn_lists, top_k, remove_bad_endings, sim, order, None, pairs)
         host = arena.cpu().numpy()                                          # the one copy
@@ -298,11 +352,19 @@ def make_reranker(corpus, method="cider", **kw):
 
 def chunk_entries(arg, h, bounds):
     """`caption_images(consensus=...)`: what every image's entry gains from `eval_collect`'s outputs `h` (None: a batch without rows)."""
+    # the search ran in the pass: every entry also carries the first k neighbour indices it used (a batch without rows launches nothing,
+    # the search included: its entries carry an empty list)
+    searched = "index" in arg
     if h is None:
-        return [{"consensus_rerank_ind": np.zeros(0, np.int64), "consensus_sim": np.zeros(0, np.float64)} for _ in bounds[1:]]
+        return [dict({"consensus_rerank_ind": np.zeros(0, np.int64), "consensus_sim": np.zeros(0, np.float64)},
+                     **({"consensus_nn": np.zeros(0, np.int64)} if searched else {})) for _ in bounds[1:]]
     k = arg.get("top_k")
     keep = [(b - a) if not k else min(b - a, int(k)) for a, b in zip(bounds, bounds[1:])]
-    return [{"consensus_rerank_ind": h["c_order"][a:a + n].astype(np.int64), "consensus_sim": h["c_sim"][a:a + n].copy()} for a, n in zip(bounds, keep)]
+    out = [{"consensus_rerank_ind": h["c_order"][a:a + n].astype(np.int64), "consensus_sim": h["c_sim"][a:a + n].copy()} for a, n in zip(bounds, keep)]
+    if searched:
+        for j, e in enumerate(out):
+            e["consensus_nn"] = h["c_nn"][j].astype(np.int64)
+    return out
 
 
 def _ngram_counters(ids):

@@ -69,6 +69,8 @@ _OPTIONS = {
     "controllability": dict(only_sct=True, att=False, covers=("index",), lacks="controllability['index'] names no first group",
                             what="controllability scores", verbs=("are", "need")),
 }
+# `consensus=` with an ImageIndex in place of the host lists: the same option, covered by the feature dict instead
+_CONSENSUS_SEARCH = dict(_OPTIONS["consensus"], covers=("features",), lacks="consensus['features'] has no feature vector")
 _NOT_IN_SCT = "not defined in sct (controllability) mode: its captions keep the input order and are not ranked"
 _ONLY_SCT = "defined only in sct (controllability) mode (eval_kwargs['sct'] = 1): they need one caption per input region set, in input order"
 
@@ -110,7 +112,8 @@ def eval_collect(score, keep, seq, bounds, identity=False, AL=None, idx=None, pi
     `idx` (the kept sub-graphs' node lists [rows, N]) are given, and ONE device -> host copy of everything.
     score [rows] fp32, keep [rows] int64, seq [rows, T] int64, bounds: python list of the I + 1 row boundaries of the images,
     pick: optional per-image subg_index list (default 0 = the best-ranked caption).
-    consensus: optional {"reranker": ConsensusReranker, "nn": per-image neighbour index lists, "top_k": int or None, "remove_bad_endings": 0 / 1}:
+    consensus: optional {"reranker": ConsensusReranker, "nn": per-image neighbour index lists, "top_k": int or None, "remove_bad_endings": 0 / 1}
+    (or, in place of "nn", "index": a neighbours.ImageIndex and "features": per-image feature vectors -> the search runs first, + c_nn):
     the ranked token rows are re-ranked on the device in the same pass (subgc_consensus_cook / _score / _rank) and, unless `pick` is
     given, the grounding launch takes each image's pick from the re-ranker's first choice ON THE DEVICE; its outputs ride in the same copy.
     -> dict of host numpy arrays: order / score / keep (int64) / seq (int64) [rows...], and with grounding att2 / node [I, T1], n_words [I];
@@ -215,6 +218,11 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
     `"consensus_sim"` (the fp64 sums of those captions).  With `return_att` the grounding entry is the re-ranker's FIRST choice, picked on
     the device in the same pass -- no second evaluation run; an explicit `grd_pick` still wins.  `remove_bad_endings` trims the
     candidates exactly as it trims the strings.  Not available in `sct` mode.
+    `consensus={"reranker": ..., "index": neighbours.ImageIndex, "features": {image_id: [D] feature vector}, "top_k": 4}` takes the place of
+    `"nn"` (exactly one of the two): the nearest-image search (`find_NNimg`) runs on the decode stream ahead of the consensus launches --
+    the batch's query rows go up with the batch, the re-ranker reads the device lists where they lie, there is no host list -- and every
+    entry additionally gains `"consensus_nn"`: the first `reranker.k` neighbour indices of its image, from the batch's one copy.
+    Optional `"k_search"` (default `reranker.k`, at most 1024) and `"workspace_bytes"` as in `ImageIndex.search`.
 
     `diversity={"scorer": DiversityScorer, "top_n": (20, 100), "seed": 2019}` (default None: off) scores every image's captions the way
     misc/diversity/diversity_score.py does -- distinct captions of a random draw, n-gram diversity, novel captions and mBLEU-4 of the
@@ -277,7 +285,11 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
         raise ValueError("caption_images: one grd_pick entry per image")
     given = {"consensus": consensus, "diversity": diversity, "accuracy": accuracy, "grounding": grounding, "controllability": controllability}
     mods = {"consensus": consensus_m, "diversity": diversity_m, "accuracy": accuracy_m, "grounding": grounding_m}
-    live = [(name, d, given[name]) for name, d in _OPTIONS.items() if given[name] is not None]
+    if consensus is not None and ("nn" in consensus) == ("index" in consensus):
+        raise ValueError("caption_images: consensus re-ranking needs exactly one of consensus['nn'] (host neighbour lists) and "
+                         "consensus['index'] (a neighbours.ImageIndex, with consensus['features'])")
+    live = [(name, _CONSENSUS_SEARCH if name == "consensus" and "index" in given[name] else d, given[name])
+            for name, d in _OPTIONS.items() if given[name] is not None]
     for name, d, opt in live:
         if sct_mode != d["only_sct"]:
             raise ValueError(f"caption_images: {d['what']} {d['verbs'][0]} " + (_ONLY_SCT if d["only_sct"] else _NOT_IN_SCT))

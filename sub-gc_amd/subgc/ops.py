@@ -11,7 +11,7 @@ import math
 
 import torch
 
-from ._lib import SubgcError, call, call_beam_att, call_consensus, call_criterion, call_decode_b16, call_gcn_agg, call_selfcritical, lib
+from ._lib import SubgcError, call, call_beam_att, call_consensus, call_criterion, call_decode_b16, call_gcn_agg, call_neighbours, call_selfcritical, lib
 from . import _scoring
 
 RELU, ACCUM = 1, 2
@@ -1835,6 +1835,32 @@ def consensus_bleu_score(cand, T, seg, I, max_cand, top_k, nn, k, cap_off, n_img
                    _ptr(nc, torch.int32), _ptr(nn_, torch.int32), _ptr(nl, torch.int32), int(n), float(fpr), int(m), int(max_caps),
                    _ptr(sim, torch.float64), _ptr(pair_out, torch.float64), 0 if pair_out is None else pair_out.stride(0), _stream())
     return sim
+
+
+NN_MAX_K = 1024         # subgc_nn_select_f64: entries of one list
+
+
+def nn_dist(q, x, dist):
+    """subgc_nn_dist_f64 (include/subgc_neighbours_hip.h): dist[i, j] = the euclidean distance of query row i and train row j in fp64 by
+    cdist's own sequential sum (consensus_reranking.py:105,113).  q [Q, D], x [N, D], dist [Q, >= N]: fp64 views with unit inner stride."""
+    for name, t in (("q", q), ("x", x), ("dist", dist)):
+        if t.dtype != torch.float64:
+            raise SubgcError(f"nn_dist: {name} is {t.dtype}; the distances are float64 like the reference's")
+    if q.size(1) != x.size(1) or dist.size(0) != q.size(0) or dist.size(1) < x.size(0):
+        raise SubgcError(f"nn_dist: q {tuple(q.shape)}, x {tuple(x.shape)}, dist {tuple(dist.shape)} do not fit together")
+    call_neighbours("subgc_nn_dist_f64", _ptr(q), ld(q), q.size(0), _ptr(x), ld(x), x.size(0), q.size(1), _ptr(dist), ld(dist), _stream())
+    return dist
+
+
+def nn_select(dist, N, k, idx, val=None):
+    """subgc_nn_select_f64: idx[i, :k] (int32) / val[i, :k] (fp64) = the k smallest of dist[i, :N] in ascending (distance, index) order
+    (np.argsort(...)[:, :num_NNimg], consensus_reranking.py:108,114; equal distances: lower index first; NaN last).  idx / val: contiguous [Q, k]."""
+    Q = dist.size(0)
+    for name, t, dt in (("idx", idx, torch.int32), ("val", val, torch.float64)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous() or tuple(t.shape) != (Q, int(k))):
+            raise SubgcError(f"nn_select: {name} must be a contiguous {dt} [{Q}, {k}] tensor, got {t.dtype} {tuple(t.shape)}")
+    call_neighbours("subgc_nn_select_f64", _ptr(dist, torch.float64), ld(dist), Q, int(N), int(k), _ptr(idx), _ptr(val), _stream())
+    return idx, val
 
 
 DIV_COLS = 8            # SUBGC_DIV_SEL: the integer columns in front of a set's selection (drawn, distinct, selected, words, unigrams, bigrams, novel, valid)
