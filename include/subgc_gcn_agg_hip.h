@@ -8,8 +8,8 @@
  * The pieces: the aggregation and its backward gather (csrc/graph.hip), a per-row scale on the fp32 GEMM's bias (csrc/gemm_f32.hip:
  * A (X W^T + 1 b^T) = (A X) W^T + rowsum(A) b^T) and the row-weighted column sums that are the bias gradients.
  *
- * A header of its own, registered in `_lib.LATER_HEADERS` (subgc_hip.h and the tables of the earlier headers keep their entry points and
- * counts).  Same library, same contract: every function returns 0 (SUBGC_OK) or a negative SUBGC_E* code with the text in
+ * A header of its own, registered in `_lib.HEADERS` (subgc_hip.h and the earlier headers keep their entry points and counts).
+ * Same library, same contract: every function returns 0 (SUBGC_OK) or a negative SUBGC_E* code with the text in
  * subgc_last_error(), never allocates device memory, never synchronises the device, enqueues on `stream` (a hipStream_t passed as void*),
  * all pointers are BORROWED device pointers, outputs are caller-allocated.  No float atomics: every sum runs in a fixed order.
  */

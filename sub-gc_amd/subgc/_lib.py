@@ -18,18 +18,14 @@ import torch  # noqa: F401  (import order matters)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include")
-# One surface per header: same library, same contract, an invoker that knows only its own declarations.  A new header is one entry here
-# and one `call_x = _invoker("x")` line below.
+# One surface per header: same library, same contract, an invoker that knows only its own declarations.  A new header is a row at the
+# end of this table, a `call_x = _invoker("x")` line below, a path constant, and a pin of its exact name set in the feature's own CPU
+# test; the table test (tests/test_headers_cpu.py) then covers it without an edit.
 HEADERS = {"core": "subgc_hip.h", "metrics": "subgc_metrics_hip.h", "grounding": "subgc_grounding_hip.h",
            "controllability": "subgc_controllability_hip.h", "criterion": "subgc_criterion_hip.h", "selfcritical": "subgc_selfcritical_hip.h",
            "consensus": "subgc_consensus_hip.h", "forced": "subgc_forced_hip.h", "control_input": "subgc_control_input_hip.h",
-           "beam_att": "subgc_beam_att_hip.h"}
-# Headers outside the table above (its keys and entry-point counts are pinned by the header tests): parsed, bound and invoked the same way.
-EXTRA_HEADERS = {"decode_b16": "subgc_decode_b16_hip.h"}
-# ... and headers added after that table was pinned in its turn: the same again.
-LATER_HEADERS = {"gcn_agg": "subgc_gcn_agg_hip.h"}
-# ... and after that one was pinned too.
-NEWER_HEADERS = {"neighbours": "subgc_neighbours_hip.h"}
+           "beam_att": "subgc_beam_att_hip.h", "decode_b16": "subgc_decode_b16_hip.h", "gcn_agg": "subgc_gcn_agg_hip.h",
+           "neighbours": "subgc_neighbours_hip.h"}
 HEADER = os.path.join(_INCLUDE, HEADERS["core"])
 METRICS_HEADER = os.path.join(_INCLUDE, HEADERS["metrics"])
 GROUNDING_HEADER = os.path.join(_INCLUDE, HEADERS["grounding"])
@@ -40,9 +36,9 @@ CONSENSUS_HEADER = os.path.join(_INCLUDE, HEADERS["consensus"])
 FORCED_HEADER = os.path.join(_INCLUDE, HEADERS["forced"])
 CONTROL_INPUT_HEADER = os.path.join(_INCLUDE, HEADERS["control_input"])
 BEAM_ATT_HEADER = os.path.join(_INCLUDE, HEADERS["beam_att"])
-DECODE_B16_HEADER = os.path.join(_INCLUDE, EXTRA_HEADERS["decode_b16"])
-GCN_AGG_HEADER = os.path.join(_INCLUDE, LATER_HEADERS["gcn_agg"])
-NEIGHBOURS_HEADER = os.path.join(_INCLUDE, NEWER_HEADERS["neighbours"])
+DECODE_B16_HEADER = os.path.join(_INCLUDE, HEADERS["decode_b16"])
+GCN_AGG_HEADER = os.path.join(_INCLUDE, HEADERS["gcn_agg"])
+NEIGHBOURS_HEADER = os.path.join(_INCLUDE, HEADERS["neighbours"])
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -55,62 +51,53 @@ class SubgcError(RuntimeError):
     pass
 
 
+def _code(path):
+    """The header's text without its comments."""
+    src = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    return re.sub(r"//[^\n]*", " ", src)
+
+
+def _declared(decl):
+    """-> (ctype, name) of one declaration, `type name` or `type* name`; pointers of any type become c_void_p."""
+    decl = " ".join(decl.split())
+    if "*" in decl:
+        return ctypes.c_void_p, decl.split("*")[-1].strip()
+    ty, nm = decl.rsplit(" ", 1)
+    return _SCALARS[ty.replace("const ", "").strip()], nm
+
+
 def parse_header(path=HEADER):
     """-> {name: (restype, [(ctype, argname), ...])} for every function the header declares."""
-    src = open(path).read()
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    src = re.sub(r"//[^\n]*", " ", src)
     out = {}
-    for m in re.finditer(r"\b(int|const\s+char\s*\*)\s+(subgc_\w+)\s*\(([^;{}]*?)\)\s*;", src, flags=re.S):
+    for m in re.finditer(r"\b(int|const\s+char\s*\*)\s+(subgc_\w+)\s*\(([^;{}]*?)\)\s*;", _code(path), flags=re.S):
         ret, name, args = m.group(1), m.group(2), m.group(3).strip()
-        protos = []
-        if args and args != "void":
-            for a in args.split(","):
-                a = " ".join(a.split())
-                if "*" in a:
-                    protos.append((ctypes.c_void_p, a.split("*")[-1].strip()))
-                else:
-                    ty, nm = a.rsplit(" ", 1)
-                    protos.append((_SCALARS[ty.replace("const ", "").strip()], nm))
+        protos = [_declared(a) for a in args.split(",")] if args and args != "void" else []
         out[name] = (ctypes.c_char_p if "char" in ret else ctypes.c_int, protos)
     return out
 
 
 def parse_struct(name, path=HEADER):
-    """ctypes.Structure mirror of `typedef struct <name> { ... } <name>;` in the header (one field per declaration; pointers of any
-    type become c_void_p): the header stays the single source of truth for the layout, like the prototypes."""
-    src = open(path).read()
-    src = re.sub(r"/\*.*?\*/", " ", src, flags=re.S)
-    src = re.sub(r"//[^\n]*", " ", src)
-    m = re.search(r"typedef\s+struct\s+" + name + r"\s*\{(.*?)\}\s*" + name + r"\s*;", src, flags=re.S)
+    """ctypes.Structure mirror of `typedef struct <name> { ... } <name>;` in the header (one field per declaration): the header stays
+    the single source of truth for the layout, like the prototypes."""
+    m = re.search(r"typedef\s+struct\s+" + name + r"\s*\{(.*?)\}\s*" + name + r"\s*;", _code(path), flags=re.S)
     if m is None:
-        raise SubgcError(f"{name} is not declared in subgc_hip.h")
-    fields = []
-    for decl in m.group(1).split(";"):
-        decl = " ".join(decl.split())
-        if not decl:
-            continue
-        if "*" in decl:
-            fields.append((decl.split("*")[-1].strip(), ctypes.c_void_p))
-        else:
-            ty, nm = decl.rsplit(" ", 1)
-            fields.append((nm, _SCALARS[ty.replace("const ", "").strip()]))
+        raise SubgcError(f"{name} is not declared in {os.path.basename(path)}")
+    fields = [(nm, ty) for ty, nm in (_declared(decl) for decl in m.group(1).split(";") if decl.strip())]
     return type(name, (ctypes.Structure,), {"_fields_": fields})
 
 
 _lib = None
-PROTOS = {}         # key of HEADERS / EXTRA_HEADERS / LATER_HEADERS / NEWER_HEADERS -> its parsed prototypes; filled once by lib()
-_protos = None      # PROTOS["core"]: what `call` checks
+PROTOS = {}         # key of HEADERS -> its parsed prototypes; filled once by lib()
 
 
 def lib():
-    global _lib, _protos
+    global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise SubgcError(f"{LIB_PATH} is missing: run `python sub-gc_amd/build.py` (hipcc, gfx950). "
                              "There is no CPU fallback for the Sub-GC hot path.")
         L = ctypes.CDLL(LIB_PATH)
-        for key, hdr in {**HEADERS, **EXTRA_HEADERS, **LATER_HEADERS, **NEWER_HEADERS}.items():
+        for key, hdr in HEADERS.items():
             PROTOS[key] = parse_header(os.path.join(_INCLUDE, hdr))
             for name, (ret, args) in PROTOS[key].items():
                 try:
@@ -119,33 +106,17 @@ def lib():
                     raise SubgcError(f"libsubgc_hip.so does not export {name} declared in {hdr}") from e
                 fn.restype = ret
                 fn.argtypes = [a for a, _ in args]
-        _protos = PROTOS["core"]
         if L.subgc_version() != 1:
             raise SubgcError("libsubgc_hip.so ABI version mismatch")
         _lib = L
     return _lib
 
 
-_FN = {}          # bound entry points (one attribute lookup on the CDLL per name instead of one per call)
-
-
-def call(name, *args):
-    """Invoke an int-returning entry point and raise on a non-zero code."""
-    fn = _FN.get(name)
-    if fn is None:
-        L = lib()
-        if name not in _protos:
-            raise SubgcError(f"{name} is not declared in subgc_hip.h")
-        fn = _FN[name] = getattr(L, name)
-    rc = fn(*args)
-    if rc != 0:
-        raise SubgcError(f"{name} failed with code {rc}: {lib().subgc_last_error().decode()}")
-
-
 def _invoker(key):
-    """`call` for the entry points of one header of HEADERS / EXTRA_HEADERS / LATER_HEADERS / NEWER_HEADERS: a cache of its own, so that no invoker reaches another's
-    declarations."""
-    cache, hdr = {}, {**HEADERS, **EXTRA_HEADERS, **LATER_HEADERS, **NEWER_HEADERS}[key]
+    """-> the invoker of one header of HEADERS: it calls an int-returning entry point by name and raises on a non-zero code.  A cache of
+    bound entry points of its own (one attribute lookup on the CDLL per name instead of one per call), so that no invoker reaches
+    another's declarations."""
+    cache, hdr = {}, HEADERS[key]
 
     def invoke(name, *args):
         fn = cache.get(name)
@@ -161,6 +132,7 @@ def _invoker(key):
     return invoke
 
 
+call = _invoker("core")
 call_metrics = _invoker("metrics")
 call_grounding = _invoker("grounding")
 call_controllability = _invoker("controllability")

@@ -1,6 +1,6 @@
-"""The nearest-image search without a GPU: its header (include/subgc_neighbours_hip.h, registered in `_lib.NEWER_HEADERS`, a fourth table
-beside the three pinned ones), the exported symbols, every host-side refusal through ctypes, and the contract in numpy
-(`neighbours.find_nn_restatement`) against the fixture the reference's own `find_NNimg` wrote (tests/golden/make_golden_neighbours.py).
+"""The nearest-image search without a GPU: its header (include/subgc_neighbours_hip.h, a row of `_lib.HEADERS`; what holds for every
+row, the invokers' refusals included, is in test_headers_cpu.py), the exported symbols, every host-side refusal through ctypes, and the
+contract in numpy (`neighbours.find_nn_restatement`) against the fixture the reference's own `find_NNimg` wrote (tests/golden/make_golden_neighbours.py).
 
 The tie rule (tests/neighbours_golden.py: compare_lists): outside groups of exactly equal distances every list position holds the
 reference's index; a group wholly inside the list holds the reference's set of indices; inside a group the order is ascending index.
@@ -19,28 +19,17 @@ META, ARR = G.load()
 CASES = sorted(META["cases"])
 
 
-def test_the_header_is_registered_in_the_fourth_table_and_nowhere_else():
-    assert _lib.NEWER_HEADERS == {"neighbours": "subgc_neighbours_hip.h"}
-    assert all("neighbours" not in t for t in (_lib.HEADERS, _lib.EXTRA_HEADERS, _lib.LATER_HEADERS))
+def test_the_header_declares_exactly_the_two_entry_points():
     assert os.path.basename(_lib.NEIGHBOURS_HEADER) == "subgc_neighbours_hip.h" and os.path.isfile(_lib.NEIGHBOURS_HEADER)
     protos = _lib.parse_header(_lib.NEIGHBOURS_HEADER)
     assert set(protos) == NAMES
     L = _lib.lib()
     assert _lib.PROTOS["neighbours"] == protos and all(hasattr(L, n) for n in NAMES)
-    others = {**_lib.HEADERS, **_lib.EXTRA_HEADERS, **_lib.LATER_HEADERS}
-    every = [set(_lib.parse_header(os.path.join(os.path.dirname(_lib.HEADER), h))) for h in others.values()]
+    every = [set(_lib.parse_header(os.path.join(os.path.dirname(_lib.HEADER), h))) for k, h in _lib.HEADERS.items() if k != "neighbours"]
+    assert len(every) == len(_lib.HEADERS) - 1 >= 12
     assert not NAMES & set().union(*every)                                  # no name is declared in two headers
     assert sum(len(e) for e in every) == len(set().union(*every))
     assert L.subgc_version() == 1
-
-
-def test_the_invoker_knows_its_own_header_only():
-    with pytest.raises(SubgcError, match="^subgc_gemm_f32 is not declared in subgc_neighbours_hip.h$"):
-        _lib.call_neighbours("subgc_gemm_f32")
-    with pytest.raises(SubgcError, match="^subgc_nn_dist_f64 is not declared in subgc_hip.h$"):
-        _lib.call("subgc_nn_dist_f64")
-    with pytest.raises(SubgcError, match="^subgc_nn_select_f64 is not declared in subgc_consensus_hip.h$"):
-        _lib.call_consensus("subgc_nn_select_f64")
 
 
 def test_host_side_refusals_need_no_gpu():
