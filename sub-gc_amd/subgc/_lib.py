@@ -25,7 +25,7 @@ HEADERS = {"core": "subgc_hip.h", "metrics": "subgc_metrics_hip.h", "grounding":
            "controllability": "subgc_controllability_hip.h", "criterion": "subgc_criterion_hip.h", "selfcritical": "subgc_selfcritical_hip.h",
            "consensus": "subgc_consensus_hip.h", "forced": "subgc_forced_hip.h", "control_input": "subgc_control_input_hip.h",
            "beam_att": "subgc_beam_att_hip.h", "decode_b16": "subgc_decode_b16_hip.h", "gcn_agg": "subgc_gcn_agg_hip.h",
-           "neighbours": "subgc_neighbours_hip.h"}
+           "neighbours": "subgc_neighbours_hip.h", "decode_rules": "subgc_decode_rules_hip.h"}
 HEADER = os.path.join(_INCLUDE, HEADERS["core"])
 METRICS_HEADER = os.path.join(_INCLUDE, HEADERS["metrics"])
 GROUNDING_HEADER = os.path.join(_INCLUDE, HEADERS["grounding"])
@@ -39,6 +39,7 @@ BEAM_ATT_HEADER = os.path.join(_INCLUDE, HEADERS["beam_att"])
 DECODE_B16_HEADER = os.path.join(_INCLUDE, HEADERS["decode_b16"])
 GCN_AGG_HEADER = os.path.join(_INCLUDE, HEADERS["gcn_agg"])
 NEIGHBOURS_HEADER = os.path.join(_INCLUDE, HEADERS["neighbours"])
+DECODE_RULES_HEADER = os.path.join(_INCLUDE, HEADERS["decode_rules"])
 LIB_PATH = os.path.join(_HERE, "libsubgc_hip.so")
 
 _SCALARS = {
@@ -145,6 +146,7 @@ call_beam_att = _invoker("beam_att")
 call_decode_b16 = _invoker("decode_b16")
 call_gcn_agg = _invoker("gcn_agg")
 call_neighbours = _invoker("neighbours")
+call_decode_rules = _invoker("decode_rules")
 
 FAM = {"gemm": 1, "attn": 2, "lstm": 3, "gcn": 4, "pool": 5, "softmax": 6}
 

@@ -258,10 +258,20 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
     per-row entries of its rows (Noun IoU with its pairs and assignments, BLEU material, CIDEr, ROUGE-L against the row's group);
     `controllability.summarize` of those entries, flattened in `order_list` order, gives the script's numbers.  `index` holds the first
     group of EVERY image of the references: an image's number of groups is the distance to the next first group (the last image's: to
-    the number of groups), and an image whose kept rows differ from it in number is an error that names the image id."""
+    the number of groups), and an image whose kept rows differ from it in number is an error that names the image id.
+
+    Decode rules (subgc.decode_rules; greedy / sampling decode only, `beam_size > 1` with one of the first three raises):
+    `eval_kwargs["block_trigrams"]` (with `"trigram_alpha"`, default 2.0), `["block_bad_endings"]` (the ids of BAD_ENDINGS are taken from
+    `ix_to_word` unless `["bad_ending_ids"]` gives them), `["suppress_unk"]` and `["decoding_constraint"]` shape the captions in the token
+    loop.  With a rule active every entry gains `"rule_stats"`: int32 [captions, 4], per caption (in the entry's caption order) the steps
+    on which a trigram penalty / the repeat ban / the bad-ending ban was applied and on which the first arg-max moved
+    (`decode_rules.STAT_NAMES`).  `remove_bad_endings` is untouched by them: it trims the finished strings."""
     import torch.distributed as dist
     from . import parallel
     eval_kwargs = dict(eval_kwargs or {})
+    if eval_kwargs.get("block_bad_endings", 0) and eval_kwargs.get("bad_ending_ids") is None:
+        from .decode_rules import bad_ending_ids
+        eval_kwargs["bad_ending_ids"] = bad_ending_ids(ix_to_word)
     world = dist.get_world_size() if dist.is_initialized() else 1
     if shard and world > 1:
         ids = [info["id"] for info in infos]
@@ -351,6 +361,7 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
             h = eval_collect(hold["score"], hold["keep"], hold["seq"], bounds, identity=not model.gpn,
                              AL=hold["AL"] if ground else None, idx=hold["idx"] if ground else None, pick=pick if ground else None, **args)
             gained = [mod.chunk_entries(args[name], h, bounds) for name, _, _, mod in batch_opts]
+            rule_stats = hold["rule_stats"].cpu().numpy() if hold.get("rule_stats") is not None else None
             for j, (k, a, b) in enumerate(zip(ids, bounds, bounds[1:])):
                 entry = {"image_id": k, "caption": decode_sequence(ix_to_word, h["seq"][a:b], rbe),
                          "subgraph_score": h["score"][a:b], "sorted_subgraph_ind": h["keep"][a:b]}
@@ -359,6 +370,8 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
                     sub = int(pick[j]) if pick is not None else (int(h["c_first"][j]) if consensus is not None else 0)
                     entry["grounding"] = {"subg_index": sub, "sort_ind": h["order"][a:b],
                                           "att2_ind": h["att2"][j, :w].astype(np.int64), "node_ind": h["node"][j, :w].astype(np.int64)}
+                if rule_stats is not None:                              # the decode rows' counters, in the entry's caption order
+                    entry["rule_stats"] = rule_stats[a:b][h["order"][a:b]]
                 for per_image in gained:
                     entry.update(per_image[j])
                 predictions.append(entry)

@@ -21,6 +21,7 @@ import torch
 from .. import beam
 from .. import functions as F_
 from .. import ops
+from ..decode_rules import DecodeRules
 
 
 def _forced_pick(logp, tok, k, temp, t, seq, seqlp, it, unfinished, counts):
@@ -34,6 +35,45 @@ def _forced_pick(logp, tok, k, temp, t, seq, seqlp, it, unfinished, counts):
     seqlp[:, t] = slp
     it.copy_(w)
     counts[t] = unf.sum().int()
+
+
+def _bad_ids_tensor(rules, dev):
+    """The bad-ending ids of an active block_bad_endings rule as a device int32 tensor, else None."""
+    if rules is None or not rules.block_bad_endings or not rules.bad_ids:
+        return None
+    return ops.upload(list(rules.bad_ids), torch.int32, dev)
+
+
+def rules_state(rules, n, dev):
+    """-> (bad-ending ids on the device or None, zeroed int32 [n, 4] counters) of an active set of rules: what `token_loop` hands to
+    `ops.decode_rules` at every step."""
+    return _bad_ids_tensor(rules, dev), ops.zero_(torch.empty(n, 4, device=dev, dtype=torch.int32))
+
+
+def token_loop(st, seq, seqlp, it, unfinished, counts, k, temp, top_p=1.0, ut=None, rules=None, bad_ids=None, stats=None, AL=None,
+               forced=None, on_step=None):
+    """The token loop of a decode batch (AttModel.py:282-319) on a decode state `st`: anything with `step(it, att_out, normalize=)`
+    that returns the step's fp32 logits [n, V + 1] (functions.DecodeState; a stand-in in tests).  T = seq.size(1) choices and one more
+    step (the attention of the last word).  `ut` [T, n]: the sampler's uniforms (k > 0); `AL` [T + 1, n, N]: attention rows.
+    `rules` (DecodeRules) active: every step is step -> `ops.decode_rules` (in place: log-softmax + rules, counters in `stats`) ->
+    the pick on the ruled row with raw=False.  Inactive: step -> pick on the raw logits, no other launch.
+    `forced` [n, T] follows a given token path (test plumbing in torch); `on_step(t, logits)` sees every step's logits (the debug tap)."""
+    T = seq.size(1)
+    active = rules is not None and rules.active
+    for t in range(T + 1):
+        logp = st.step(it, None if AL is None else AL[t], normalize=forced is not None)
+        if on_step is not None:
+            on_step(t, logp)
+        if t == T:
+            break
+        prev = counts[t - 1:t] if t > 0 else None
+        if forced is not None:
+            _forced_pick(logp, forced[:, t].contiguous(), k, temp, t, seq, seqlp, it, unfinished, counts)
+            continue
+        if active:
+            ops.decode_rules(logp, seq, t, rules.flags, rules.trigram_pen, bad_ids, stats, prev)
+        ops.decode_pick(logp, k, temp, None if ut is None else ut[t], t, seq, seqlp, it, unfinished, counts[t:t + 1], prev,
+                        raw=not active, top_p=top_p)
 
 
 def score_candidates(m, X2, N, images, fb=None):
@@ -214,12 +254,13 @@ class _GraphedLoop:
     The reference-shaped call decodes <= 10 rows per step: ~12 kernels of 5-30 us each, 21 steps -- launch-bound.  For a
     given row count the launch sequence is static (the early break is device-side), so it is captured once on buffers
     of fixed address and replayed per image; the image's prepared features are written into those buffers first.
-    Keyed by (rows, N, attention rows capacity, k, the_p, return_att) and by the version of the flat parameter buffer (the
+    Keyed by (rows, N, attention rows capacity, k, the_p, the decode rules, return_att) and by the version of the flat parameter buffer (the
     K-concatenated LSTM weights inside DecodeState are snapshots of the parameters).  Every launch inside the graph and around the
     replay is a C-ABI kernel: the small state tensors live in one arena (one zero fill, one snapshot copy per image)."""
 
-    def __init__(self, m, n, N, k, return_att, P, fb=None, top_p=1.0):
+    def __init__(self, m, n, N, k, return_att, P, fb=None, top_p=1.0, rules=None):
         dev = m.flat_params.device
+        self.rules = rules if (rules is not None and rules.active) else None
         T, R, A, L = m.seq_length, m.rnn_size, m.att_hid_size, m.GCN_dim
         self.n, self.N, self.T, self.k, self.return_att = n, N, T, k, return_att
         self.top_p = top_p
@@ -229,7 +270,12 @@ class _GraphedLoop:
         # results first (seq, keep_out, seqlp, score_out: snapshot as one block), then the loop's scratch state
         self.arena, v, sp = _arena(dev, [("seq", (n, T), torch.long), ("keep_out", (n,), torch.long), ("it", (n,), torch.long),
                                          ("seqlp", (n, T), torch.float32), ("score_out", (n,), torch.float32),
-                                         ("unfinished", (n,), torch.int32), ("counts", (T,), torch.int32)])
+                                         ("unfinished", (n,), torch.int32), ("counts", (T,), torch.int32)]
+                                   + ([("rule_stats", (n, 4), torch.int32)] if self.rules is not None else []))
+        # active rules: the counters sit in the arena (zeroed with it); the bad-ending ids are a device tensor of fixed address
+        self.rule_stats = v.get("rule_stats")
+        self.bad_ids = _bad_ids_tensor(self.rules, dev)
+        self.stats_out = None
         self.views, self.result_words = v, sp["score_out"][0] + sp["score_out"][1]
         self.seq, self.seqlp, self.it, self.unfinished, self.counts = v["seq"], v["seqlp"], v["it"], v["unfinished"], v["counts"]
         self.score_out, self.keep_out = v["score_out"], v["keep_out"]
@@ -255,16 +301,13 @@ class _GraphedLoop:
         if self.fb is not None:
             self.fb.prepared(self.m, self.n, self.P, self)
         self.st.reset()
-        if self.k == 0 and self.st.fused and self.st.xt_table is not None and getattr(self.m, "decode_fused_pick", True):
+        if self.rules is None and self.k == 0 and self.st.fused and self.st.xt_table is not None and getattr(self.m, "decode_fused_pick", True):
             # greedy: the pick rides in the logits / attention-LSTM launches (functions.DecodeState.greedy_loop)
             self.st.greedy_loop(T, self.seq, self.seqlp, self.counts, self.AL, self.it)
             return
-        for t in range(T + 1):
-            logp = self.st.step(self.it, self.AL[t] if self.return_att else None, normalize=False)
-            if t == T:
-                break
-            ops.decode_pick(logp, self.k, self.topk_temp, None if self.u is None else self.u[t], t, self.seq, self.seqlp, self.it,
-                            self.unfinished, self.counts[t:t + 1], self.counts[t - 1:t] if t > 0 else None, raw=True, top_p=self.top_p)
+        # the generic step -> pick loop; with active rules the rules launch sits between the two and the fused greedy loop is never taken
+        token_loop(self.st, self.seq, self.seqlp, self.it, self.unfinished, self.counts, self.k, self.topk_temp, self.top_p, self.u,
+                   self.rules, self.bad_ids, self.rule_stats, self.AL if self.return_att else None)
 
     def run(self, pr, uniforms, step_major=False):
         """-> (seq, seqlp, counts, AL, score_out, keep_out): the results are one snapshot copy of the arena's result block.
@@ -288,6 +331,8 @@ class _GraphedLoop:
         AL = None
         if self.AL is not None:
             AL = ops.copy_(torch.empty_like(self.AL), self.AL)
+        if self.rule_stats is not None:
+            self.stats_out = ops.copy_(torch.empty_like(self.rule_stats), self.rule_stats)
         return seq, seqlp, self.counts, AL, score_out, keep_out
 
 
@@ -352,16 +397,17 @@ def _graphed_beam(m, n, N, P, opt, fb=None, return_att=False):
     return cache[key]
 
 
-def _graphed_loop(m, n, N, k, return_att, P, fb=None):
+def _graphed_loop(m, n, N, k, return_att, P, fb=None, rules=None):
     top_p = m.the_p if k else 1.0
-    key = (n, N, (k, top_p, m.decode_b16_on()), return_att, None if fb is None else fb.G) + m.weights_version()
+    rkey = None if rules is None else rules.key
+    key = (n, N, (k, top_p, m.decode_b16_on()) + (() if rkey is None else (rkey,)), return_att, None if fb is None else fb.G) + m.weights_version()
     cache = m.__dict__.setdefault("_graph_cache", {})
     if key not in cache:
         for old in [q for q in cache if q[:5] == key[:5]]:                       # parameters changed: drop the stale snapshot
             del cache[old]
         if len(cache) >= 64:                                                      # states share their weight snapshots: a graph is a few MB
             cache.clear()
-        cache[key] = _GraphedLoop(m, n, N, k, return_att, P, fb, top_p)
+        cache[key] = _GraphedLoop(m, n, N, k, return_att, P, fb, top_p, rules)
     return cache[key]
 
 
@@ -373,6 +419,8 @@ def decode_one_image(m, X2, N, image, opt, uniforms=None, forced=None):
     T = m.seq_length
     beam_size = opt.get("beam_size", 1)
     return_att = opt.get("return_att", 0) == 1
+    rules = DecodeRules.from_options(opt)                                         # (refuses the rules beam search does not know)
+    m.__dict__["rule_stats"] = None                                               # the last decode's counters [rows, 4], when a rule is active
     graphable = m.gpn and not m.sct and forced is None and getattr(m, "decode_hipgraph", True) and m.__dict__.get("tap") is None
     G_in = int(image[1].size(1) * image[1].size(2)) if m.gpn else 0
     fb = _front_buffers(m, G_in, N) if (graphable and G_in > 0) else None
@@ -391,7 +439,7 @@ def decode_one_image(m, X2, N, image, opt, uniforms=None, forced=None):
         # fewer sub-graphs survived, the surplus rows decoded stale candidates and are cut off, and the log-probs the reference would not
         # have written after ITS early break (AttModel.py:318-319: taken over the real rows only) are zeroed (subgc_decode_batch_finish).
         try:
-            g = _graphed_loop(m, n_spec, N, k, False, m._decoder_params(), fb)
+            g = _graphed_loop(m, n_spec, N, k, False, m._decoder_params(), fb, rules)
         except RuntimeError as e:
             import warnings
             warnings.warn(f"hipGraph capture of the decode loop failed ({e}); decoding eagerly from now on")
@@ -407,6 +455,8 @@ def decode_one_image(m, X2, N, image, opt, uniforms=None, forced=None):
         seq, seqlp, _, _, score_out, keep_out = g.run(None, _uniforms(m, n_spec, T, X2.device) if k else None, step_major=True)
         arrived.synchronize()
         n = int(host_n[0])
+        if n > 0 and g.stats_out is not None:
+            m.__dict__["rule_stats"] = g.stats_out[:n]
         if n == n_spec:
             return (seq, seqlp, score_out, keep_out)
         if n == 0:
@@ -433,13 +483,14 @@ def decode_one_image(m, X2, N, image, opt, uniforms=None, forced=None):
         own_u = bool(k) and uniforms is None
         if own_u:
             uniforms = _uniforms(m, n, T, X2.device)                              # step-major [T, n]
-        g = _graphed_loop(m, n, N, k, return_att, P, fb)
+        g = _graphed_loop(m, n, N, k, return_att, P, fb, rules)
     except RuntimeError as e:                                                     # capture unavailable here: same kernels, launched eagerly
         import warnings
         warnings.warn(f"hipGraph capture of the decode loop failed ({e}); decoding eagerly from now on")
         m.decode_hipgraph = False
         return decode(m, X2, N, select_subgraphs(m, X2, N, [image], front=fr, kept=[n]), opt, uniforms, forced)[0]
     seq, seqlp, counts, AL, score_out, keep_out = g.run(None, uniforms, step_major=own_u if k else False)
+    m.__dict__["rule_stats"] = g.stats_out
     r = (seq, seqlp, score_out, keep_out)
     if return_att:
         dead = (counts.cpu() == 0).nonzero()
@@ -474,6 +525,8 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
     T = m.seq_length
     return_att = opt.get("return_att", 0) == 1
     beam_size = opt.get("beam_size", 1)
+    rules = DecodeRules.from_options(opt)                                              # (refuses the rules beam search does not know)
+    m.__dict__["rule_stats"] = stats = None
     sizes = [s["keep"].numel() for s in sel]
     n = sum(sizes)
     z = lambda *s, dt=torch.float32: ops.zero_(torch.empty(*s, device=dev, dtype=dt))
@@ -532,13 +585,14 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
     if len(sel) == 1 and forced is None and n <= 16 and getattr(m, "decode_hipgraph", True) and tap is None:
         # the reference-shaped call (one image, <= 10 rows): launch-bound, replayed as one hipGraph
         try:
-            graphed = _graphed_loop(m, n, N, k, return_att, P)
+            graphed = _graphed_loop(m, n, N, k, return_att, P, rules=rules)
         except RuntimeError as e:                                                # capture unavailable here: same kernels, launched eagerly
             import warnings
             warnings.warn(f"hipGraph capture of the decode loop failed ({e}); decoding eagerly from now on")
             m.decode_hipgraph = False
     if graphed is not None:
         seq, seqlp, counts, AL, _, _ = graphed.run(pr, uniforms, step_major=own_u)
+        stats = graphed.stats_out
     else:
         st = F_.DecodeState(pr, P, N, return_att, xt_table=m.xt_gates_table(), fuse_lstm=True, snapshots=m.decode_snapshots(), W16=m.decode_w16(), b16_batched=m.decode_b16_on())
         seq, seqlp, it = z(n, T, dt=torch.long), z(n, T), z(n, dt=torch.long)
@@ -552,20 +606,18 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
             if AL is None:
                 AL = z(T + 1, n, N)
             steps_tap = {k: [] for k in ("h_att", "h_lang", "c_att", "c_lang", "alpha", "logp")}
-        for t in range(T + 1):
-            logp = st.step(it, AL[t] if (return_att or tap is not None) else None, normalize=forced is not None)
-            if tap is not None:                                                        # state after core step t, in the oracle's names
+        on_step = None
+        if tap is not None:                                                            # state after core step t, in the oracle's names
+            def on_step(t, logp):
                 R = st.R
                 for key_, v_ in (("h_att", st.H1[:, R:]), ("h_lang", st.H1[:, :R]), ("c_att", st.C1[0]), ("c_lang", st.C2[0]), ("alpha", AL[t]),
                                  ("logp", logp if forced is not None else torch.log_softmax(logp, 1))):
                     steps_tap[key_].append(v_.clone())
-            if t == T:
-                break
-            if forced is not None:
-                _forced_pick(logp, forced[:, t].contiguous(), k, m.topk_temp, t, seq, seqlp, it, unfinished, counts)
-            else:
-                ops.decode_pick(logp, k, m.topk_temp, None if ut is None else ut[t], t, seq, seqlp, it,
-                                unfinished, counts[t:t + 1], counts[t - 1:t] if t > 0 else None, raw=True, top_p=m.the_p if k else 1.0)
+        bad_ids = None
+        if rules.active and forced is None:
+            bad_ids, stats = rules_state(rules, n, dev)
+        token_loop(st, seq, seqlp, it, unfinished, counts, k, m.topk_temp, m.the_p if k else 1.0, ut, rules, bad_ids, stats,
+                   AL if (return_att or tap is not None) else None, forced, on_step)
     if tap is not None and graphed is None:
         tap.update({"step_" + key_: torch.stack(v_, 0) for key_, v_ in steps_tap.items()})
         if not return_att:
@@ -588,6 +640,9 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
     if batch_out is not None:
         skip_att = bool(batch_out.pop("skip_att", False))
         batch_out.update(_batch_view(sel, whole, seq, seqlp, AL if return_att else None, idx_k, lens_k, bounds))
+        if stats is not None:
+            batch_out["rule_stats"] = stats                                            # int32 [rows, 4]: decode_rules.STAT_NAMES
+    m.__dict__["rule_stats"] = stats
     out = []
     for i, (s, a, b) in enumerate(zip(sel, bounds, bounds[1:])):
         r = (seq[a:b], seqlp[a:b], s["score"], s["keep"])

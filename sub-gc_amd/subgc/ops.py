@@ -11,7 +11,7 @@ import math
 
 import torch
 
-from ._lib import SubgcError, call, call_beam_att, call_consensus, call_criterion, call_decode_b16, call_gcn_agg, call_neighbours, call_selfcritical, lib
+from ._lib import SubgcError, call, call_beam_att, call_consensus, call_criterion, call_decode_b16, call_decode_rules, call_gcn_agg, call_neighbours, call_selfcritical, lib
 from . import _scoring
 
 RELU, ACCUM = 1, 2
@@ -1670,6 +1670,21 @@ def decode_sample(logits, k, top_p, temp, u, t, seq, seqlp, next_tok, unfinished
     call("subgc_decode_sample", _ptr(logits), ld(logits), n, V, int(k), float(top_p), float(temp), _ptr(u), int(t), _ptr(seq, torch.int64),
          _ptr(seqlp), seq.size(1), _ptr(next_tok, torch.int64), _ptr(unfinished, torch.int32), _ptr(n_unf, torch.int32),
          _ptr(prev_count, torch.int32), int(raw), _stream())
+
+
+def decode_rules(logits, seq, t, flags, trigram_pen, bad_ids=None, stats=None, prev_count=None):
+    """The decode rules of step t, in place on the fp32 logits rows [n, V] (subgc_decode_rules; include/subgc_decode_rules_hip.h): the
+    rows become their log-softmax with block_trigrams / suppress_unk / decoding_constraint / block_bad_endings (`flags`) applied from
+    the history seq[:, :t].  `bad_ids`: device int32 ids; `stats`: int32 [n, 4] counters or None.  The pick then runs with raw=False."""
+    n, V = logits.shape
+    if seq.dim() != 2 or seq.size(0) != n or not seq.is_contiguous():
+        raise SubgcError(f"decode_rules: seq must be a contiguous [n, T] tensor with n = {n} rows, got {tuple(seq.shape)}")
+    if stats is not None and (tuple(stats.shape) != (n, 4) or not stats.is_contiguous()):
+        raise SubgcError(f"decode_rules: stats must be a contiguous [{n}, 4] tensor, got {tuple(stats.shape)}")
+    call_decode_rules("subgc_decode_rules", _ptr(logits, torch.float32), ld(logits), n, V, _ptr(seq, torch.int64), seq.size(1), int(t), int(flags),
+                      float(trigram_pen), _ptr(bad_ids, torch.int32), 0 if bad_ids is None else bad_ids.numel(), _ptr(stats, torch.int32),
+                      _ptr(prev_count, torch.int32), _stream())
+    return logits
 
 
 def row_topk(x, k, vals, idx, log_softmax=True):
