@@ -12,7 +12,9 @@
  * search applies the repeat ban and the UNK penalty (CaptionModel.py:128-131).  The rules sit where the upstream project this model
  * descends from applies them: on the log-probabilities of a step, between AttModel.py:289 (get_logprobs_state) and :295 (the choice).
  * No atomics of any kind; every sum and every count has a fixed order, so equal inputs give equal bits.
- * Out of scope: beam search under these rules, the self-critical rollout, forced decode.
+ * Beam search calls the same entry point with rules 1 and 4 alone (eval_kwargs["beam_rules"]): every state row's history is the words of
+ * the beam that occupies it, word w of beam group g in column g + w behind g columns of -1, and the top-k reads the ruled row.
+ * Out of scope: the self-critical rollout, forced decode.
  */
 #ifndef SUBGC_DECODE_RULES_HIP_H
 #define SUBGC_DECODE_RULES_HIP_H

@@ -14,8 +14,11 @@ the fork "beam q -> slot vix" is one row gather of the recurrent state.
 Why beam+2 columns are enough: a group's augmented row differs from the raw one only at the UNK column
 (-1000, CaptionModel.py:137), at the previous word (decoding_constraint, :134-135) and at the <= beam-bdash
 distinct words the earlier groups picked (:33-40), all of which only move DOWN; the top bdash of the
-augmented row therefore lie within the top (bdash + those) <= beam+2 of the raw row.
+augmented row therefore lie within the top (bdash + those) <= beam+2 of the raw row.  Under `beam_rules` (block_trigrams and the
+bad-ending ban per beam) "the raw row" is the RULED row -- `subgc_decode_rules` rewrites the logits row in place
+before the top-k reads it -- so the same argument holds word for word.
 """
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
@@ -38,6 +41,68 @@ def penalty_builder(cfg):
     if kind == "avg":
         return lambda length, logprob: logprob / length
     raise ValueError(f"unknown length_penalty {cfg!r} (expected '', 'wu_<alpha>' or 'avg_<alpha>')")
+
+
+# What `search` hands to an engine's `first` / `advance` under beam_rules: `rules` (DecodeRules), `words` int64 [rows, T] (row r: the
+# words of the beam that occupies state row r, unshifted, -1 behind its length), `length` int [rows] and `t` = the decoder step about
+# to be ruled (0: <bos>; loop iteration i feeds step i + 1) and `columns` = T + group_size - 1, the width of the device layout.  A live
+# row of group g has length t - g.
+RuleHistory = namedtuple("RuleHistory", "rules words length t columns")
+
+
+def shifted_history(words, length, t, Th):
+    """The device layout of the histories of one step: int64 [rows, Th], row r = (t - length[r]) times -1, then its words, then -1:
+    word w of a group-g row sits in column g + w, so ONE step number t serves every live group in `subgc_decode_rules`."""
+    words, length = np.asarray(words, np.int64), np.asarray(length, np.int64)
+    out = np.full((words.shape[0], Th), -1, np.int64)
+    for r in range(words.shape[0]):
+        L = int(length[r])
+        if L > t:
+            raise ValueError(f"beam rules: row {r} holds {L} words before step {t}")
+        out[r, t - L:t] = words[r, :L]
+    return out
+
+
+def check_rule_limits(T, G):
+    """The history of a state row has T + G - 1 columns and is staged in LDS by `subgc_decode_rules` (SUBGC_RULES_MAX_T)."""
+    if T + G - 1 > 64:
+        raise ValueError(f"beam_rules: the history of a state row takes T + group_size - 1 = {T + G - 1} columns; the limit is 64")
+
+
+def ruled_topk(logits, kk, history, bufs):
+    """The top-k of one step of the host `search` over an engine's logits [rows, V1] on the device -> (values, indices) as numpy
+    [rows, kk].  `history` None: `subgc_row_topk_f32` folds the log-softmax in.  A RuleHistory: the two launches of `DeviceSearch.loop`
+    -- `subgc_decode_rules` on the shifted histories (in place on `logits`), then the top-k of the ruled rows with log_softmax = 0.
+    `bufs`: a dict the caller keeps for the life of its engine; the output buffers and the uploaded bad-ending ids live there."""
+    rows, dev = logits.size(0), logits.device
+    if "vals" not in bufs:
+        bufs["vals"] = torch.empty(rows, kk, device=dev, dtype=torch.float32)
+        bufs["idx"] = torch.empty(rows, kk, device=dev, dtype=torch.int32)
+    vals, idx = bufs["vals"], bufs["idx"]
+    if history is None:
+        ops.row_topk(logits, kk, vals, idx, log_softmax=True)
+    else:
+        rules = history.rules
+        if "bad_ids" not in bufs:
+            bufs["bad_ids"] = ops.upload(list(rules.bad_ids), torch.int32, dev) if (rules.block_bad_endings and rules.bad_ids) else None
+        hist = torch.from_numpy(shifted_history(history.words, history.length, history.t, history.columns)).to(dev)
+        ops.decode_rules(logits, hist, history.t, rules.flags, rules.trigram_pen, bufs["bad_ids"], None, None)
+        ops.row_topk(logits, kk, vals, idx, log_softmax=False)
+    return vals.cpu().numpy(), idx.cpu().numpy()
+
+
+def _active(rules):
+    return rules if (rules is not None and rules.active) else None
+
+
+def _beam_events(rules, seq_row, length):
+    from .decode_rules import sequence_events                                 # (decode_rules imports eval_glue: not at module load)
+    return sequence_events(seq_row, length, rules)
+
+
+def winners_rule_stats(done_beams):
+    """int32 [n, 4] (a CPU tensor): the "rule_stats" of every sub-graph's winning beam, done_beams[s][0]."""
+    return torch.from_numpy(np.stack([np.asarray(b[0]["rule_stats"], np.int32) for b in done_beams]).reshape(-1, 4))
 
 
 class _Group:
@@ -101,24 +166,21 @@ class _BatchEngine:
                                    W16=W16, b16_batched=b16_batched)                  # default: no twins, beam search streams the fp32 weights
         self.V1 = self.st.V1
         self.alpha = torch.empty(self.rows, N, device=dev, dtype=torch.float32) if return_att else None    # host `search`: the last step's rows
+        self.topk_bufs = {}                                                      # `ruled_topk`'s outputs (and the uploaded bad-ending ids)
 
     def refresh(self):
         """Re-derive the per-beam rows from `pr` and restart the recurrent state (hipGraph replay: `pr` was overwritten in place)."""
         ops.take_rows([(self.pr.f, self.prb.f), (self.pr.off, self.prb.off), (self.pr.lens, self.prb.lens)], self.rep)      # one launch
         self.st.reset()
 
-    def _topk(self, logits, kk):
-        if not hasattr(self, "vals"):
-            self.vals = torch.empty(self.rows, kk, device=self.dev, dtype=torch.float32)
-            self.idx = torch.empty(self.rows, kk, device=self.dev, dtype=torch.int32)
-        ops.row_topk(logits, kk, self.vals, self.idx, log_softmax=True)
-        return self.vals.cpu().numpy(), self.idx.cpu().numpy()
+    def _topk(self, logits, kk, history=None):
+        return ruled_topk(logits, kk, history, self.topk_bufs)
 
-    def first(self, kk):                                                         # <bos>, AttModel.py:223-227
-        return self._topk(self.st.step(torch.zeros(self.rows, device=self.dev, dtype=torch.long), self.alpha, normalize=False), kk)
+    def first(self, kk, history=None):                                           # <bos>, AttModel.py:223-227
+        return self._topk(self.st.step(torch.zeros(self.rows, device=self.dev, dtype=torch.long), self.alpha, normalize=False), kk, history)
 
-    def advance(self, tok, kk):
-        return self._topk(self.st.step(torch.from_numpy(tok).to(self.dev), self.alpha, normalize=False), kk)
+    def advance(self, tok, kk, history=None):
+        return self._topk(self.st.step(torch.from_numpy(tok).to(self.dev), self.alpha, normalize=False), kk, history)
 
     def attention(self):
         """[rows, N] attention rows of the step `first` / `advance` just ran (host `search` with return_att)."""
@@ -155,10 +217,17 @@ class _StepEngine:
         ops.row_topk(logp.float().contiguous(), kk, vals, idx, log_softmax=False)
         return vals.cpu().numpy(), idx.cpu().numpy()
 
-    def first(self, kk):
+    _NO_RULES = ("beam_rules: the step-API engine (get_logprobs_state) hands over log-probabilities its caller computed and cannot rule "
+                 "them; decode through mode='sample' / sample_images")
+
+    def first(self, kk, history=None):
+        if history is not None:
+            raise ValueError(self._NO_RULES)
         return self._topk(self.logp, kk)
 
-    def advance(self, tok, kk):
+    def advance(self, tok, kk, history=None):
+        if history is not None:
+            raise ValueError(self._NO_RULES)
         logp, self.state = self.m.get_logprobs_state(torch.from_numpy(tok).to(self.dev), *self.args, self.state)
         return self._topk(logp, kk)
 
@@ -180,7 +249,7 @@ class _StepEngine:
 
 
 @torch.no_grad()
-def beam_decode(pr, P, N, T, opt, xt_table=None, on_device=True, return_att=False, W16=None, b16_batched=False):
+def beam_decode(pr, P, N, T, opt, xt_table=None, on_device=True, return_att=False, W16=None, b16_batched=False, rules=None):
     """Decode every sub-graph of `pr` (an F_.Prepared) with beam search.
     Returns (seq [n, T] int64, seqLogprobs [n, T] fp32, done_beams) -- CPU tensors, as the reference's are.
     `on_device` (default): the candidate bookkeeping runs in `subgc_beam_step`, the loop has no host round trip;
@@ -188,9 +257,11 @@ def beam_decode(pr, P, N, T, opt, xt_table=None, on_device=True, return_att=Fals
     `return_att`: a fourth element {"AL": fp32 [T + 1, n, N] (device tensor; numpy from the host `search`), "len": int array [n]}: the
     attention rows of every sub-graph's winning beam, AL[w, s] = the distribution of the decoder step whose logits produced word w of
     seq[s], zero for w >= len[s] (len counts the end token and is T for a beam cut at the last step).  Beam search never feeds its last
-    word (CaptionModel.py:170-171), so unlike a greedy decode there is no attention row behind the last word: AL[T] is all zero."""
+    word (CaptionModel.py:170-171), so unlike a greedy decode there is no attention row behind the last word: AL[T] is all zero.
+    `rules` (DecodeRules.from_beam_options, active): every step's rows are ruled before the top-k reads them and
+    every kept beam gains "rule_stats"; on the host path through the same two launches, so the two agree bit for bit."""
     eng = _BatchEngine(pr, P, N, int(opt.get("beam_size", 10)), xt_table, return_att=return_att, W16=W16, b16_batched=b16_batched)
-    return search_device(eng, T, opt, return_att) if on_device else search(eng, T, opt, return_att)
+    return search_device(eng, T, opt, return_att, rules) if on_device else search(eng, T, opt, return_att, rules)
 
 
 def check_picks(pick, cnt):
@@ -271,10 +342,14 @@ def _check(opt, eng):
 class DeviceSearch:
     """`search` with the per-step bookkeeping in `subgc_beam_step`: every step is top-k -> beam step -> state gather ->
     decoder step on the stream (`loop`: launches only, no host read, so it can be captured in a hipGraph); the host reads
-    the finished beams once, after the last step (`collect`)."""
+    the finished beams once, after the last step (`collect`).
+    `rules` (active): every decoder step is followed by `subgc_decode_rules` on the rows' histories, which live on the device as two
+    ping-pong int64 buffers [rows, T + G - 1] (word w of group g in column g + w, -1 elsewhere), forked with the state's `src` after
+    every beam step; the top-k then reads the ruled rows with log_softmax = 0.  The launch sequence stays static."""
 
-    def __init__(self, eng, T, opt, return_att=False):
+    def __init__(self, eng, T, opt, return_att=False, rules=None):
         self.eng, self.T, self.opt = eng, T, dict(opt)
+        self.rules = _active(rules)
         self.beam, self.G, self.bd, self.kk = _check(opt, eng)
         self.lam = float(_F32(opt.get("diversity_lambda", 0.5)))
         self.constraint = opt.get("decoding_constraint", 0)
@@ -297,6 +372,36 @@ class DeviceSearch:
             self.nv, self.ni = torch.empty_like(self.tv), torch.empty_like(self.ti)
             base = torch.arange(rows, device=dev).view(n, G, bd)
             self.group_rows = [base[:, g].reshape(-1).contiguous() for g in range(G)]
+        self.hist = self.hist_now = None
+        if self.rules is not None:
+            check_rule_limits(T, G)
+            Th = self.Th = T + G - 1
+            self.bad_ids = None
+            if self.rules.block_bad_endings and self.rules.bad_ids:
+                self.bad_ids = ops.upload(list(self.rules.bad_ids), torch.int32, dev)
+            # the constant template (all -1) and the two copies that ping-pong; `loop` starts from the template, so a replay starts clean
+            self.hist0 = torch.empty(rows, Th, device=dev, dtype=torch.long)     # (one uploaded row, gathered into every row)
+            ops.take_rows([(ops.upload([-1] * Th, torch.int64, dev).view(1, Th), self.hist0)], ops.zero_(torch.empty(rows, device=dev, dtype=torch.long)))
+            self.hist = [torch.empty_like(self.hist0), torch.empty_like(self.hist0)]
+            if G > 1:                                                             # column t belongs to the groups that are live at iteration t
+                g_of = (torch.arange(rows, device=dev) // bd) % G
+                t_of = torch.arange(Th, device=dev).view(Th, 1)
+                self.live_rows = ((g_of <= t_of) & (t_of <= T - 1 + g_of)).contiguous()
+
+    def _fork_history(self, cur, t):
+        """history[row] <- history[src[row]], then column t <- the step's `tok` for the rows of the groups that stepped (a sleeping
+        group's tok of 0 is not written: its column keeps -1).  G == 1: two C-ABI launches on the 4-byte word views."""
+        a, b = self.hist[cur], self.hist[1 - cur]
+        ops.gather_rows(ops._words(a), self.src, ops._words(b))
+        if self.G == 1:
+            ops.copy2d(ops._words(self.tok.view(-1, 1)), ops._words(b)[:, 2 * t:2 * t + 2])
+        else:
+            b[:, t] = torch.where(self.live_rows[t], self.tok, self.hist0[:, t])
+        return 1 - cur
+
+    def _rule(self, logits, cur, t):
+        r = self.rules
+        ops.decode_rules(logits, self.hist[cur], t, r.flags, r.trigram_pen, self.bad_ids, None, None)
 
     def loop(self, fresh_tables=False):
         eng, T, G, bd, kk, tb = self.eng, self.T, self.G, self.bd, self.kk, self.tb
@@ -307,12 +412,20 @@ class DeviceSearch:
                 ops.zero_(x)
         att = self.AL_step
         step = ops.beam_step_anc if att is not None else ops.beam_step
-        ops.row_topk(eng.st.step(tok, None if att is None else att[0], normalize=False), kk, tv, ti, log_softmax=True)      # <bos>, AttModel.py:223-227
+        ruled = self.rules is not None                                           # the top-k then reads log-probabilities (log_softmax = 0)
+        logits = eng.st.step(tok, None if att is None else att[0], normalize=False)                                         # <bos>, AttModel.py:223-227
+        if ruled:
+            now = 0                                                              # which of the two history copies is current
+            ops.copy_(self.hist[0], self.hist0)
+            self._rule(logits, now, 0)
+        ops.row_topk(logits, kk, tv, ti, log_softmax=not ruled)
         if G > 1:
             init = eng.snapshot()
             tv4, ti4, nv4, ni4 = (x.view(n, G, bd, kk) for x in (tv, ti, self.nv, self.ni))
         for t in range(T + G - 1):
             step(tv, ti, tb, tok, src, t, T, G, bd, kk, unk, self.constraint, self.lam)
+            if ruled:
+                now = self.hist_now = self._fork_history(now, t)
             if not any(g <= t + 1 <= T + g - 1 for g in range(G)):
                 break
             if G > 1 and 0 < t < G:                                               # group t starts now: give it the post-<bos> state
@@ -321,10 +434,12 @@ class DeviceSearch:
                     cur.index_copy_(0, sel, saved.index_select(0, sel))
             eng.st.reorder(src)
             logits = eng.st.step(tok, None if att is None else att[t + 1], normalize=False)
+            if ruled:
+                self._rule(logits, now, t + 1)
             if G == 1:
-                ops.row_topk(logits, kk, tv, ti, log_softmax=True)
+                ops.row_topk(logits, kk, tv, ti, log_softmax=not ruled)
             else:
-                ops.row_topk(logits, kk, self.nv, self.ni, log_softmax=True)
+                ops.row_topk(logits, kk, self.nv, self.ni, log_softmax=not ruled)
                 for g in range(G):
                     if g <= t <= T + g - 1:                                       # only the groups that stepped take the new rows
                         tv4[:, g], ti4[:, g] = nv4[:, g], ni4[:, g]
@@ -356,6 +471,12 @@ class DeviceSearch:
         per = G * bd
         done_beams = [[{"seq": rs[k], "logps": rl[k], "unaug_p": top_un[k], "p": top_p[k]} for k in range(s * per, (s + 1) * per)]
                       for s in range(n)]
+        if self.rules is not None:                                                    # every kept beam's counters, from its own words
+            from .decode_rules import sequence_events_rows
+            ev = sequence_events_rows(top_seq.reshape(-1, T).numpy(), np.take_along_axis(dlen, order, -1).reshape(-1), self.rules)
+            for s in range(n):
+                for k, b in enumerate(done_beams[s]):
+                    b["rule_stats"] = ev[s * per + k]
         seq, seqlp = top_seq[:, 0, 0].clone(), top_lps[:, 0, 0].clone()
         if not self.return_att:
             return seq, seqlp, done_beams
@@ -372,15 +493,19 @@ class DeviceSearch:
 
 
 @torch.no_grad()
-def search_device(eng, T, opt, return_att=False):
-    ds = DeviceSearch(eng, T, opt, return_att)
+def search_device(eng, T, opt, return_att=False, rules=None):
+    ds = DeviceSearch(eng, T, opt, return_att, rules)
     ds.loop(fresh_tables=True)
     return ds.collect()
 
 
 @torch.no_grad()
-def search(eng, T, opt, return_att=False):
+def search(eng, T, opt, return_att=False, rules=None):
     """The bookkeeping of CaptionModel.beam_search (:97-176) over an engine that owns the recurrent state.
+    `rules` (DecodeRules.from_beam_options, active): before every `first` / `advance` the words of the beam that occupies each state row
+    (after the fork; unshifted, per group) go to the engine as `history=RuleHistory(...)`, and the engine rules its rows -- log-softmax,
+    then block_trigrams and the bad-ending ban of `subgc_decode_rules` -- before its top-k; every kept beam gains "rule_stats"
+    (`decode_rules.sequence_events`).  Inactive or None: the engines are called exactly as before.
     `return_att`: the engine also answers `attention()` ([rows, N] of the step it just ran); every kept beam gains "att" (fp32 [len, N]:
     the attention row of the step whose logits produced each of its words, backtracked through the beam's ancestry: word 0 from the
     <bos> step, word w >= 1 of group g from the step of loop iteration w + g - 1 at the row of the slot the beam held after word
@@ -402,7 +527,14 @@ def search(eng, T, opt, return_att=False):
     if bd > kk:
         raise ValueError("beam wider than the vocabulary")
     shape = (n, G, bd, kk)
-    tv, ti = (x.reshape(shape).copy() for x in eng.first(kk))
+    rules = _active(rules)
+    if rules is not None:
+        check_rule_limits(T, G)
+        words, length = np.full((n, G, bd, T), -1, np.int64), np.zeros((n, G, bd), np.int64)
+        hist = lambda step: {"history": RuleHistory(rules, words.reshape(rows, T), length.reshape(rows), step, T + G - 1)}
+    else:
+        hist = lambda step: {}
+    tv, ti = (x.reshape(shape).copy() for x in eng.first(kk, **hist(0)))
     att_steps = [np.array(eng.attention(), np.float32)] if return_att else None     # slice 0: <bos>; slice t + 1: iteration t's step
     init = eng.snapshot() if G > 1 else None
     groups = [[_Group(T, bd) for _ in range(G)] for _ in range(n)]
@@ -424,6 +556,8 @@ def search(eng, T, opt, return_att=False):
                         final["p"] = length_penalty(tau + 1, final["p"])
                         if return_att:
                             final.update(anc=grp.anc[:tau + 1, vix].copy(), len=tau + 1, rows=base[s, g].copy(), shift=g)
+                        if rules is not None:
+                            final["rule_stats"] = _beam_events(rules, grp.seq[:, vix], tau + 1)
                         grp.done.append(final)
                         grp.sums[vix] = -1000
                 tok[s, g] = grp.seq[tau]
@@ -432,7 +566,13 @@ def search(eng, T, opt, return_att=False):
         if G > 1 and 0 < t < G:                                                  # group t starts now: give it the post-<bos> state
             eng.restore(base[:, t].reshape(-1), init)
         eng.reorder(src.reshape(-1))
-        nv, ni = (x.reshape(shape) for x in eng.advance(tok.reshape(-1), kk))
+        if rules is not None:                                                    # the rows' beams after the fork: t + 1 - g words of group g
+            length[:] = 0
+            for g in live:
+                for s in range(n):
+                    words[s, g, :, :t - g + 1] = groups[s][g].seq[:t - g + 1].T
+                length[:, g] = t - g + 1
+        nv, ni = (x.reshape(shape) for x in eng.advance(tok.reshape(-1), kk, **hist(t + 1)))
         if return_att:
             att_steps.append(np.array(eng.attention(), np.float32))
         for g in live:

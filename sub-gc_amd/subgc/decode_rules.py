@@ -7,6 +7,10 @@ Here the rules act on the log-probabilities of a step, between AttModel.py:289 a
 
 `DecodeRules` is the host-side description (hashable: it keys the graph caches); `apply_rules_restatement` restates the contract in
 numpy with an fp64 log-softmax -- what the tests compare the kernel with, and the host loop of the stand-in states.
+
+Beam search takes block_trigrams and the bad-ending ban per beam through `eval_kwargs["beam_rules"]` (`DecodeRules.from_beam_options`;
+`beam.DeviceSearch` / `beam.search` rule every state row before the top-k reads it); `sequence_events` counts what the rules did
+along one beam.
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ MAX_BAD_IDS = 64                      # SUBGC_RULES_MAX_BAD
 FLAG_TRIGRAMS, FLAG_UNK, FLAG_REPEAT, FLAG_BAD_END = 1, 2, 4, 8
 STAT_NAMES = ("trigram", "repeat", "bad_ending", "changed")
 BEAM_REFUSED = ("block_trigrams", "block_bad_endings", "suppress_unk")
+BEAM_RULE_KEYS = ("block_trigrams", "trigram_alpha", "block_bad_endings", "bad_ending_ids")   # eval_kwargs["beam_rules"]
 
 
 def bad_ending_ids(ix_to_word):
@@ -83,7 +88,8 @@ class DecodeRules:
             for name in BEAM_REFUSED:
                 if opt.get(name, 0):
                     raise ValueError(f"{name} = {opt[name]} with beam_size = {opt['beam_size']}: the decode rules act on the greedy / "
-                                     "sampling loop only (beam search honours decoding_constraint alone)")
+                                     "sampling loop only (beam search honours decoding_constraint alone; block_trigrams and "
+                                     "block_bad_endings under beam search go into eval_kwargs['beam_rules'])")
             return cls()
         ids = ()
         if opt.get("block_bad_endings", 0):
@@ -97,6 +103,70 @@ class DecodeRules:
         return cls(block_trigrams=opt.get("block_trigrams", 0) or 0, trigram_alpha=opt.get("trigram_alpha", 2.0),
                    decoding_constraint=opt.get("decoding_constraint", 0) or 0, block_bad_endings=opt.get("block_bad_endings", 0) or 0,
                    suppress_unk=opt.get("suppress_unk", 0) or 0, bad_ids=ids)
+
+
+    @classmethod
+    def from_beam_options(cls, opt, ix_to_word=None):
+        """The rules of `eval_kwargs["beam_rules"]`: a dict with the keys block_trigrams, trigram_alpha, block_bad_endings and
+        bad_ending_ids (or `ix_to_word`), honoured by beam search only.  -> a DecodeRules with at most the trigram and bad-ending
+        flags set (inactive when the key is absent).  Same limits and messages as `from_options`; beam_size <= 1, a
+        decoding_constraint / suppress_unk entry (beam search has its own repeat ban, the top-level decoding_constraint, and always
+        applies the UNK penalty) and unknown keys raise."""
+        opt = opt or {}
+        br = opt.get("beam_rules")
+        if br is None:
+            return cls()
+        if not isinstance(br, dict):
+            raise ValueError(f"beam_rules must be a dict with keys among {BEAM_RULE_KEYS}, got {type(br).__name__}")
+        beam = int(opt.get("beam_size", 1) or 1)
+        if beam <= 1:
+            raise ValueError(f"beam_rules with beam_size = {beam}: the key is honoured by beam search only; the greedy / sampling loop "
+                             "takes the top-level keys block_trigrams, trigram_alpha, block_bad_endings and bad_ending_ids")
+        for name in ("decoding_constraint", "suppress_unk"):
+            if name in br:
+                raise ValueError(f"beam_rules['{name}']: beam search has its own repeat ban (the top-level decoding_constraint) and "
+                                 "always applies the UNK penalty; beam_rules takes " + ", ".join(BEAM_RULE_KEYS))
+        unknown = sorted(k for k in br if k not in BEAM_RULE_KEYS)
+        if unknown:
+            raise ValueError(f"beam_rules: unknown key(s) {unknown}; it takes " + ", ".join(BEAM_RULE_KEYS))
+        ids = ()
+        if br.get("block_bad_endings", 0):
+            if br.get("bad_ending_ids") is not None:
+                ids = tuple(int(i) for i in br["bad_ending_ids"])
+            elif ix_to_word is not None:
+                ids = bad_ending_ids(ix_to_word)
+            else:
+                raise ValueError("block_bad_endings needs the ids of the bad endings: pass eval_kwargs['beam_rules']['bad_ending_ids'] "
+                                 "(decode_rules.bad_ending_ids(ix_to_word)) or the vocabulary")
+        return cls(block_trigrams=br.get("block_trigrams", 0) or 0, trigram_alpha=br.get("trigram_alpha", 2.0),
+                   block_bad_endings=br.get("block_bad_endings", 0) or 0, bad_ids=ids)
+
+
+def sequence_events(seq_row, length, rules):
+    """The counters of ONE beam under `beam_rules`, from its own words: int32 [4] in STAT_NAMES order -- the number of steps
+    0 .. length - 1 at which a trigram penalty applied (the words before the step repeat their last two somewhere earlier, followed by
+    a word >= 0), 0, the number of steps at which the bad-ending ban applied (the word before is a listed id), and -1: "the first
+    arg-max moved" is undefined under beam search."""
+    return sequence_events_rows(np.asarray(seq_row).reshape(1, -1), [int(length)], rules)[0]
+
+
+def sequence_events_rows(seqs, lengths, rules):
+    """`sequence_events` of many beams at once: seqs int [m, T], lengths int [m] -> int32 [m, 4]."""
+    h = np.asarray(seqs, np.int64)
+    m, T = h.shape
+    L = np.minimum(np.asarray(lengths, np.int64).reshape(m), T)
+    out = np.zeros((m, 4), np.int32)
+    out[:, 3] = -1
+    for t in range(1, T):
+        step = t < L                                                  # the beam has a word t, chosen from the row ruled at step t
+        if rules.block_trigrams and t >= 3:
+            hit = np.zeros(m, bool)
+            for j in range(t - 2):
+                hit |= (h[:, j] == h[:, t - 2]) & (h[:, j + 1] == h[:, t - 1]) & (h[:, j + 2] >= 0)
+            out[:, 0] += hit & step
+        if rules.block_bad_endings and rules.bad_ids:
+            out[:, 2] += np.isin(h[:, t - 1], rules.bad_ids) & step
+    return out
 
 
 def trigram_counts(h, t, V):

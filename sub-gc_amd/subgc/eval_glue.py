@@ -265,13 +265,21 @@ def caption_images(model, images, infos, ix_to_word, eval_kwargs=None, group=256
     `ix_to_word` unless `["bad_ending_ids"]` gives them), `["suppress_unk"]` and `["decoding_constraint"]` shape the captions in the token
     loop.  With a rule active every entry gains `"rule_stats"`: int32 [captions, 4], per caption (in the entry's caption order) the steps
     on which a trigram penalty / the repeat ban / the bad-ending ban was applied and on which the first arg-max moved
-    (`decode_rules.STAT_NAMES`).  `remove_bad_endings` is untouched by them: it trims the finished strings."""
+    (`decode_rules.STAT_NAMES`).  `remove_bad_endings` is untouched by them: it trims the finished strings.
+    Under beam search the two rules that have a beam meaning come in through `eval_kwargs["beam_rules"]`, a dict with the keys
+    `block_trigrams`, `trigram_alpha`, `block_bad_endings` and `bad_ending_ids` (filled from `ix_to_word` the same way;
+    `DecodeRules.from_beam_options`): every state row is ruled before the top-k reads it, and `"rule_stats"` holds
+    `decode_rules.sequence_events` of every caption's winning beam (columns 1 and 3 are 0 and -1 there)."""
     import torch.distributed as dist
     from . import parallel
     eval_kwargs = dict(eval_kwargs or {})
     if eval_kwargs.get("block_bad_endings", 0) and eval_kwargs.get("bad_ending_ids") is None:
         from .decode_rules import bad_ending_ids
         eval_kwargs["bad_ending_ids"] = bad_ending_ids(ix_to_word)
+    br = eval_kwargs.get("beam_rules")
+    if isinstance(br, dict) and br.get("block_bad_endings", 0) and br.get("bad_ending_ids") is None:
+        from .decode_rules import bad_ending_ids
+        eval_kwargs["beam_rules"] = dict(br, bad_ending_ids=bad_ending_ids(ix_to_word))
     world = dist.get_world_size() if dist.is_initialized() else 1
     if shard and world > 1:
         ids = [info["id"] for info in infos]

@@ -343,7 +343,7 @@ class _GraphedBeam:
     `return_att`: the step-major attention buffer and the ancestry tables are static and filled inside the graph; the gather of the
     winners' rows needs the host's ranking and runs after the replay, outside the graph (`DeviceSearch.collect`)."""
 
-    def __init__(self, m, n, N, P, opt, fb=None, return_att=False):
+    def __init__(self, m, n, N, P, opt, fb=None, return_att=False, rules=None):
         dev = m.flat_params.device
         T, R, A, L = m.seq_length, m.rnn_size, m.att_hid_size, m.GCN_dim
         self.m, self.n, self.P, self.fb = m, n, P, fb
@@ -357,7 +357,7 @@ class _GraphedBeam:
         b16 = m.decode_b16_on()                                                  # on: the bf16 twins reach the engine (<= 32 rows: the fused bf16 regimes)
         self.eng = beam._BatchEngine(self.pr, P, N, int(opt.get("beam_size", 10)), m.xt_gates_table(), m.decode_snapshots(), return_att=return_att,
                                      W16=m.decode_w16() if b16 else None, b16_batched=b16)
-        self.ds = beam.DeviceSearch(self.eng, T, opt, return_att)
+        self.ds = beam.DeviceSearch(self.eng, T, opt, return_att, rules)          # rules (beam_rules): their launches ride in the graph
         self._loop()                                                             # eager warm-up
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
@@ -383,9 +383,11 @@ def _beam_graph_rows(m):
     return 32 if m.decode_b16_on() else 128
 
 
-def _graphed_beam(m, n, N, P, opt, fb=None, return_att=False):
+def _graphed_beam(m, n, N, P, opt, fb=None, return_att=False, rules=None):
     okey = tuple(sorted((k, v) for k, v in opt.items() if k in ("beam_size", "group_size", "diversity_lambda", "decoding_constraint", "length_penalty")))
     okey += (("return_att", bool(return_att)), ("b16_batched", m.decode_b16_on()))
+    if rules is not None and rules.active:
+        okey += (("beam_rules", rules.key),)
     key = ("beam", n, N, okey, None if fb is None else fb.G) + m.weights_version()
     cache = m.__dict__.setdefault("_graph_cache", {})
     if key not in cache:
@@ -393,7 +395,7 @@ def _graphed_beam(m, n, N, P, opt, fb=None, return_att=False):
             del cache[old]
         if len(cache) >= 64:                                                      # states share their weight snapshots: a graph is a few MB
             cache.clear()
-        cache[key] = _GraphedBeam(m, n, N, P, opt, fb, return_att)
+        cache[key] = _GraphedBeam(m, n, N, P, opt, fb, return_att, rules)
     return cache[key]
 
 
@@ -420,6 +422,7 @@ def decode_one_image(m, X2, N, image, opt, uniforms=None, forced=None):
     beam_size = opt.get("beam_size", 1)
     return_att = opt.get("return_att", 0) == 1
     rules = DecodeRules.from_options(opt)                                         # (refuses the rules beam search does not know)
+    brules = DecodeRules.from_beam_options(opt)                                   # eval_kwargs["beam_rules"]: beam search only
     m.__dict__["rule_stats"] = None                                               # the last decode's counters [rows, 4], when a rule is active
     graphable = m.gpn and not m.sct and forced is None and getattr(m, "decode_hipgraph", True) and m.__dict__.get("tap") is None
     G_in = int(image[1].size(1) * image[1].size(2)) if m.gpn else 0
@@ -470,10 +473,12 @@ def decode_one_image(m, X2, N, image, opt, uniforms=None, forced=None):
     P = m._decoder_params()
     try:
         if beam_size > 1:
-            g = _graphed_beam(m, n, N, P, opt, fb, return_att)
+            g = _graphed_beam(m, n, N, P, opt, fb, return_att, brules)
             res = g.run(None)
             seq, seqlp, done = res[:3]
             m.done_beams = done
+            if brules.active:
+                m.__dict__["rule_stats"] = beam.winners_rule_stats(done)
             r = (seq, seqlp, ops.copy_(torch.empty_like(g.score_out), g.score_out), ops.copy_(torch.empty_like(g.keep_out), g.keep_out))
             if return_att:                                                        # [rows, steps, n_max] like the greedy path; steps = the longest beam
                 steps, n_max = int(res[3]["len"].max()), int(g.pr.lens.max().item())
@@ -526,6 +531,7 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
     return_att = opt.get("return_att", 0) == 1
     beam_size = opt.get("beam_size", 1)
     rules = DecodeRules.from_options(opt)                                              # (refuses the rules beam search does not know)
+    brules = DecodeRules.from_beam_options(opt)                                        # eval_kwargs["beam_rules"]: beam search only
     m.__dict__["rule_stats"] = stats = None
     sizes = [s["keep"].numel() for s in sel]
     n = sum(sizes)
@@ -549,7 +555,7 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
         graphed = None
         if len(sel) == 1 and n * beam_size <= _beam_graph_rows(m) and getattr(m, "decode_hipgraph", True):
             try:
-                graphed = _graphed_beam(m, n, N, P, opt, return_att=return_att)
+                graphed = _graphed_beam(m, n, N, P, opt, return_att=return_att, rules=brules)
             except RuntimeError as e:                                            # capture unavailable here: same kernels, launched eagerly
                 import warnings
                 warnings.warn(f"hipGraph capture of the beam search failed ({e}); searching eagerly from now on")
@@ -559,8 +565,10 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
         else:
             b16 = m.decode_b16_on()
             res = beam.beam_decode(pr, P, N, T, opt, xt_table=m.xt_gates_table(), return_att=return_att, W16=m.decode_w16() if b16 else None,
-                                   b16_batched=b16)
+                                   b16_batched=b16, rules=brules)
         seq, seqlp, done = res[:3]
+        if brules.active:                                                              # the winners' counters, int32 [rows, 4] on the host
+            m.__dict__["rule_stats"] = stats = beam.winners_rule_stats(done)
         m.done_beams = done if len(sel) == 1 else [done[a:b] for a, b in zip(bounds, bounds[1:])]
         AL = res[3]["AL"] if return_att else None
         skip_att = False
@@ -570,6 +578,8 @@ def decode(m, X2, N, sel, opt, uniforms=None, forced=None, batch_out=None):
             # the glue's launches (ranking, grounding arg-max) read the token rows on the device; the search hands them back on the host
             view["seq"] = ops.upload(seq.numpy().ravel(), torch.int64, dev).view(n, T)
             batch_out.update(view)
+            if stats is not None:
+                batch_out["rule_stats"] = stats
         out = [(seq[a:b], seqlp[a:b], s["score"], s["keep"]) for s, a, b in zip(sel, bounds, bounds[1:])]
         if return_att and not skip_att:
             h_lens, b_len = lens_k.cpu().numpy(), res[3]["len"]

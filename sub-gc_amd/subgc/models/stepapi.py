@@ -76,5 +76,6 @@ def beam_search(m, init_state, init_logprobs, *args, **kwargs):
     `beam_size` rows, the state after <bos> and its log-probs.  Returns the list of finished beams (`done_beams`)."""
     opt = kwargs["opt"]
     eng = beam_mod._StepEngine(m, init_state, init_logprobs, tuple(args[:4]))
-    _, _, done = beam_mod.search(eng, m.seq_length, opt)
+    from ..decode_rules import DecodeRules
+    _, _, done = beam_mod.search(eng, m.seq_length, opt, rules=DecodeRules.from_beam_options(opt))     # (active rules: the engine refuses)
     return done[0]
