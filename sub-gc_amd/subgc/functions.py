@@ -314,6 +314,25 @@ class GatherRowsFn(Function):
         return dt, None
 
 
+class ReplicateRowsFn(Function):
+    """Rows of an ACTIVATION gathered by int32 row ids (the n-fold replicas of a one-pass self-critical step): GatherRowsFn's two launches
+    for a table that is no leaf -- the backward adds the replicas' gradient rows with subgc_scatter_add_rows into a zeroed buffer."""
+
+    @staticmethod
+    def forward(ctx, x, rows):
+        x = x.contiguous()
+        out = torch.empty(rows.numel(), x.size(1), device=x.device, dtype=torch.float32)
+        ops.gather_rows(x, rows, out)
+        ctx.save_for_backward(rows)
+        ctx.shape = x.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (rows,) = ctx.saved_tensors
+        return ops.scatter_add_rows(dout.contiguous(), rows, ops.zeros(*ctx.shape, device=dout.device)), None
+
+
 class ClassTableFn(Function):
     """Linear(Embedding[cls]) for class ids (AttModel.py:374-377, 383-386: `obj_emb_proj(sg_obj_embed(argmax))`,
     `pred_emb_prj(sg_pred_embed(argmax))`): the projection is applied to the TABLE once -- table = Emb W^T + b, [classes, L] --
@@ -1092,10 +1111,23 @@ class DecoderFn(Function):
         # t >= 1 then depends on step t-1's distribution, so embeddings / x->gates / logits are produced step by step.
         # The sampled words are constants of the graph (the reference detaches them): the backward is unchanged.
         ss = meta.get("ss")
+        # one-pass self-critical step (subgc/selfcritical.py): meta["sc_onepass"] = {"n", "scorer", "d_index", "u" [T-1, S] or
+        # "tokens" [S, T-1], "stats"}.  Every row samples its own input word from the previous step's raw logits (subgc_sc_pick, all S rows
+        # draw), so this forward is the rollout and the replay's forward at once; `labels` only gives the shape until the loop has run.
+        sc = meta.get("sc_onepass")
+        if sc is not None and (ss is not None or T < 2):
+            raise ops.SubgcError(f"one-pass self-critical step: no scheduled sampling beside it and at least one sampled word per row (T = {T})")
+        stepwise = ss is not None or sc is not None
         tokens = labels if ss is None else labels[:, :T].clone()
+        if sc is not None:
+            zi = lambda *s, dt: ops.zero_(torch.empty(*s, device=dev, dtype=dt))
+            # 2 S rows: the upper half receives the picks, the lower half stays zero and only completes subgc_sc_prepare's "2 S rows"
+            sc_buf = zi(2 * S, T - 1, dt=torch.long) if sc.get("tokens") is None else torch.cat([sc["tokens"], torch.zeros_like(sc["tokens"])])
+            sc_seq, sc_lp = sc_buf[:S], zi(S, T - 1, dt=torch.float32)
+            sc_it, sc_unf = zi(S, dt=torch.long), zi(S, dt=torch.int32)
         xt = act(T, S, E)
         Gx = torch.empty(T * S, 4 * R, device=dev, dtype=torch.float32)
-        if ss is None:
+        if not stepwise:
             for t in range(T):
                 ops.embed_fwd(emb, labels[:, t], labels.stride(0), None if k_xt is None else k_xt[t], scale, xt[t])
             ops.gemm(xt.view(T * S, E), W[9][:, 2 * R:], Gx, tb=True)
@@ -1119,7 +1151,7 @@ class DecoderFn(Function):
         logits = torch.empty(S * T, V1, device=dev, dtype=torch.float32)
         logits3 = logits.view(S, T, V1)
         rec = None
-        if ss is None and T > 0 and ops.recurrence_ok():
+        if not stepwise and T > 0 and ops.recurrence_ok():
             # the T steps as ONE library call (subgc_recurrence_fwd; see functions_packed.py): every step owns all S rows
             ldh = Hout.stride(1)
             rec = ops.Recurrence(S=S, T=T, R=R, A=A, n_alpha=N, bf16=int(bf), gemm_flags=ops.GEMM_MODES[ops.gemm_mode.current], keep_scale=float(scale),
@@ -1136,6 +1168,14 @@ class DecoderFn(Function):
                     ops.multinomial_rows_(logits3[:, t - 1, :], ss[2][t], ss[1][t], ss[0], tokens[:, t])
                 ops.embed_fwd(emb, tokens[:, t], tokens.stride(0), None if k_xt is None else k_xt[t], scale, xt[t])
                 ops.gemm(xt[t], W[9][:, 2 * R:], Gx3[t], tb=True)
+            elif sc is not None:
+                if t >= 1:
+                    ops.gemm(Hout[:, t - 1, :], W[21], logits3[:, t - 1, :], tb=True, bias=lg_b)    # the logits the criterion differentiates
+                    if sc.get("tokens") is None:          # all S rows draw; a finished row keeps feeding 0 (subgc_sc_pick's filing rule)
+                        ops.sc_pick(logits3[:, t - 1, :], S, 1.0, sc["u"][t - 1], t - 1, sc_seq, sc_lp, sc_it, sc_unf, None, None, raw=True)
+                fed = (sc_it, 1) if (t == 0 or sc.get("tokens") is None) else (sc_seq[:, t - 1], sc_seq.stride(0))
+                ops.embed_fwd(emb, fed[0], fed[1], None if k_xt is None else k_xt[t], scale, xt[t])
+                ops.gemm(xt[t], W[9][:, 2 * R:], Gx3[t], tb=True)
             z0 = ops.ZERO_STATE_SKIP and t == 0                 # the state entering step 0 is zero: no product against it (recurrent.hip)
             if z0:
                 ops.lstm_fwd(Gx3[t], Gf, None, b1i, b1h, C1[t], C1[t + 1], H2[t][:, R:2 * R], H1[t + 1][:, R:], None, 1.0, None, G1[t], S, R,
@@ -1148,10 +1188,19 @@ class DecoderFn(Function):
             kz = 2 * R if z0 else 3 * R
             ops.lstm_fwd_gemm(H2[t][:, :kz], Wc2[:, :kz], pre, None, None, b2i, b2h, C2[t], C2[t + 1], H1[t + 1][:, :R], H2[t + 1][:, 2 * R:],
                               None if k_out is None else k_out[t], scale, Hout[:, t, :], G2[t], S, R)
-        if ss is None:
+        if not stepwise:
             ops.gemm(ops.flat_rows(Hout), W[21], logits, tb=True, bias=lg_b)
         else:
             ops.gemm(Hout[:, T - 1, :], W[21], logits3[:, T - 1, :], tb=True, bias=lg_b)
+        crit, reward = meta.get("crit"), meta.get("reward")
+        if sc is not None:
+            # still no host read: the replay's labels [0, row, 0] and RewardCriterion's mask of every row, the scored rows of all 2 S
+            # (the zero half is not scored), the n I segments of the accuracy kernels, the leave-one-out reward (enqueue_loo)
+            scorer = sc["scorer"]
+            labels, crit_mask, rows = ops.sc_prepare(sc_buf, V1, scorer.refs.eos_id)
+            reward, mean_reward, scores, baseline = scorer.enqueue_loo(rows, S, sc["d_index"], sc["n"])
+            crit, tokens = (labels[:, 1:], crit_mask), labels
+            sc["stats"].update(reward=mean_reward, seq=sc_seq, seqlp=sc_lp, scores=scores, baseline=baseline, rewards=reward)
         active = ops.step_active(labels, T)
         ops.log_softmax_rows_(logits, active)
 
@@ -1162,10 +1211,9 @@ class DecoderFn(Function):
             tap.update(step_h_att=f32(H2[:T, :, R:2 * R]), step_ctx=f32(H2[:T, :, :R]), step_h_lang=f32(H1[1:T + 1, :, :R]),
                        step_c_att=C1[1:].clone(), step_c_lang=C2[1:].clone(), step_alpha=AL.clone(),
                        step_logp=logits3.permute(1, 0, 2).clone(), fed_tokens=tokens[:, :T].t().clone())
-        crit = meta.get("crit")                      # (target [S,T] view, mask [S,T] view): criterion fused in
-        if crit is not None:
+        if crit is not None:                         # (target [S,T] view, mask [S,T] view): criterion fused in
             # smoothed: rows after the early break are zero rows (`active`): lp = 0, so a masked-in one adds m * H, as in the reference
-            rule = ops.Criterion(meta.get("smoothing", 0.0), meta.get("reward"))      # misc/utils.py:126-156 / 89-109 ([S,T] view)
+            rule = ops.Criterion(meta.get("smoothing", 0.0), reward)                  # misc/utils.py:126-156 / 89-109 ([S,T] view)
             _, slp = rule.row_pass(logits, raw=False)
             loss, nll_scratch = rule.fwd(logits.view(S, T, V1), crit[0], crit[1], slp)
         else:

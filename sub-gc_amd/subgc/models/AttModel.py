@@ -143,7 +143,9 @@ class AttModel(CaptionModel):
         self._dropout_calls = 0
         self.injected_masks = None       # tests inject {'fc','att','xt','out','gpn_hid'} keep-masks here
         self.injected_sc = None          # tests inject the rollout tokens [2 * b5, T] of a self-critical step (sampled half first)
-        self.sc_stats = None             # left by a self-critical step: {"reward": mean reward (device scalar), "seq": rollout tokens}
+        self.injected_sc_u = None        # tests: the uniforms [T, n * b5] of a one-pass self-critical step (sc_samples >= 2) in place of its Philox stream
+        self.sc_stats = None             # left by a self-critical step: {"reward": mean reward (device scalar), "seq": rollout tokens}; a one-pass step
+                                         # (sc_samples = n >= 2; `injected_sc` is then [n * b5, T]) adds "seqlp", "scores", "baseline", "rewards"
         self.injected_ss = None          # tests inject (selector uniforms [T,S], draw uniforms [T,S]) for scheduled sampling
         # debug tap (tests only): set to a dict and the next `model(...)` / `_sample` call files its intermediates there under the
         # oracle's / golden files' names (fusion_x, gcn_x_layer{l}, x_obj_out, read_out, att_sel, fc_sel, p_fc, p_att, pp_att,
@@ -726,7 +728,8 @@ class AttModel(CaptionModel):
         gives the batch's shape) with RewardCriterion (misc/utils.py:89-109) fused in its place: `self.fused_lang_loss` is the reward
         loss, `self.sc_stats = {"reward": mean reward, "seq": the rollout's tokens}`.  The decoder's four dropout masks have p = 0 and
         scheduled sampling is off in such a step, so the policy that is differentiated is the policy that sampled; `label_smoothing`
-        does not apply.  `self.injected_sc` [2 * b5, T] replaces the rollout's tokens (test plumbing, like `injected_ss`)."""
+        does not apply.  `self.injected_sc` [2 * b5, T] replaces the rollout's tokens (test plumbing, like `injected_ss`).
+        `self_critical=(reward, indices, n)` with n >= 2 is the one-pass step with n samples per caption row (`_forward_sc_onepass`)."""
         B, N, _ = att_feats.shape
         dev = att_feats.device
         self.__dict__.pop("_grads_are_zero", None)      # a backward may follow: "the optimizer left the gradient buffer zeroed" ends here
@@ -767,9 +770,12 @@ class AttModel(CaptionModel):
             sel_idx = c["ar_b5"]
             lens = ops.row_count(mask_sel)
         reward = None
+        sc_n = int(self_critical[2]) if self_critical is not None and len(self_critical) > 2 else 1
+        if sc_n >= 2:
+            return self._forward_sc_onepass(self_critical[0], self_critical[1], sc_n, seq, fc, Xb, lens, sel_idx, img_s, N, tap, gpn_loss, score)
         if self_critical is not None:
             from .. import selfcritical
-            scorer, d_index = self_critical
+            scorer, d_index = self_critical[:2]
             seq2 = self.injected_sc
             if seq2 is None:
                 seq2 = selfcritical.rollout(self, fc, Xb, lens, sel_idx, img_s, N, T=T_roll)
@@ -817,6 +823,47 @@ class AttModel(CaptionModel):
         outputs, lang_loss = F_.DecoderFn.apply(meta, seq.contiguous(), fc, Xb, lens, sel_idx, img_s, *self._decoder_params())
         self.fused_lang_loss = lang_loss if fused_crit is not None else None
         return outputs, gpn_loss, score
+
+    def _forward_sc_onepass(self, scorer, d_index, n, seq, fc, Xb, lens, sel_idx, img_s, N, tap, gpn_loss, score):
+        """The self-critical step with n >= 2 samples per caption row and the leave-one-out baseline, in ONE decoder pass:
+        the decoder Function runs S = n b5 rows, sample-major (row k b5 + s is sample k of caption row s), and samples its own input
+        words (functions.DecoderFn.forward, `sc_onepass`).  `fc`, `lens`, `sel_idx` and `img_s` are replicated n-fold by the package's
+        gather launches (the replicas' d(fc) rows are summed by subgc_scatter_add_rows); the node states are not: every replica packs
+        its own attention set out of the one `Xb`, as functions.Prepared does for any row, and prepared_backward scatter-adds d(Xb).
+        `self.injected_sc` [n b5, T] makes the loop follow given tokens, `self.injected_sc_u` [T, n b5] replaces its uniforms."""
+        from .. import selfcritical
+        dev = fc.device
+        b5, T_roll = seq.size(0), seq.size(1) - 2
+        S = n * b5
+        selfcritical.SelfCriticalReward.check_steps(T_roll)
+        key = ("sc_rep", str(dev), b5, n)
+        rep = self.__dict__.setdefault("_const_cache", {}).get(key)
+        if rep is None:
+            rep = self.__dict__["_const_cache"][key] = ops.upload(list(range(b5)) * n, torch.int32, dev)
+        fc_n = F_.ReplicateRowsFn.apply(fc, rep)
+        lens_n, idx_n, img_n = (ops.gather_rows_words(t.contiguous(), rep) for t in (lens, sel_idx, img_s))
+        inj, u = self.injected_sc, None
+        if inj is not None:
+            if tuple(inj.shape) != (S, T_roll) or inj.dtype != torch.int64:
+                raise ops.SubgcError(f"injected_sc: int64 tokens [n * b5, T] = [{S}, {T_roll}], got {inj.dtype} {tuple(inj.shape)}")
+            inj = inj.contiguous()
+        else:
+            u = self.injected_sc_u
+            if u is None:
+                u = selfcritical.onepass_uniforms(self, T_roll, S, dev)
+            elif tuple(u.shape) != (T_roll, S):
+                raise ops.SubgcError(f"injected_sc_u: step-major uniforms [T, n * b5] = [{T_roll}, {S}], got {tuple(u.shape)}")
+            u = u.contiguous()
+        stats = {}
+        meta = {"N": N, "p": 0.0, "masks": {}, "crit": (), "plan": None, "tap": tap,
+                "sc_onepass": {"n": n, "scorer": scorer, "d_index": d_index, "u": u, "tokens": inj, "stats": stats}}
+        if self.bf16_storage:
+            flat16 = self.weights_b16()
+            meta["W16"] = [self.W16(k, flat16) for k in F_.PARAM_ORDER]
+        shape_only = torch.empty(S, T_roll + 2, device=dev, dtype=torch.int64)        # the Function fills its own labels [0, sampled row, 0]
+        _, self.fused_lang_loss = F_.DecoderFn.apply(meta, shape_only, fc_n, Xb, lens_n, idx_n, img_n, *self._decoder_params())
+        self.sc_stats = stats
+        return None, gpn_loss, score
 
     # ------------------------------------------------------------------ decode
     def _sample_sentences(self, *args, **kwargs):

@@ -43,10 +43,15 @@ class RewardCriterion(torch.nn.Module):
 
 
 class LossWrapper(torch.nn.Module):
-    def __init__(self, model, opt, sc_reward=None):
-        """`sc_reward`: a subgc.selfcritical.SelfCriticalReward; with it `forward(..., sc_flag=True)` is a self-critical step."""
+    def __init__(self, model, opt, sc_reward=None, sc_samples=None):
+        """`sc_reward`: a subgc.selfcritical.SelfCriticalReward; with it `forward(..., sc_flag=True)` is a self-critical step.
+        `sc_samples` (default: `opt.train_sample_n`, else 1): the samples per caption row of such a step.  1: the rollout with its greedy
+        baseline and the replay, every launch as before; 2 .. 16: one decoder pass over n samples per row, each sample's baseline the
+        mean score of the others (subgc/selfcritical.py); anything else raises ValueError."""
         super().__init__()
+        from ..selfcritical import check_samples
         self.sc_reward = sc_reward
+        self.sc_samples = check_samples(getattr(opt, "train_sample_n", 1) if sc_samples is None else sc_samples)
         self.opt = opt
         self.model = model
         # `opt` may be None (the benchmark and the tools) or lack the attribute: LanguageModelCriterion, every launch as before
@@ -92,5 +97,5 @@ class LossWrapper(torch.nn.Module):
             d_index = ops.upload(idx, torch.int32, att_feats.device)
         _, gpn_loss, _ = self.model(fc_feats, att_feats, labels, att_masks, trip_pred, obj_dist, obj_box, rel_ind, pred_fmap, pred_dist,
                                     gpn_obj_ind, gpn_pred_ind, gpn_nrel_ind, gpn_pool_mtx, need_outputs=False,
-                                    self_critical=(self.sc_reward, d_index))
+                                    self_critical=(self.sc_reward, d_index) if self.sc_samples == 1 else (self.sc_reward, d_index, self.sc_samples))
         return {"gpn_loss": gpn_loss, "lang_loss": self.model.fused_lang_loss, "reward": self.model.sc_stats["reward"]}

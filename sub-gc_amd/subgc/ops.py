@@ -1957,6 +1957,15 @@ def gather_rows(src, rows, dst, m_dev=None):
     return dst
 
 
+def gather_rows_words(src, rows):
+    """out[m] = src[rows[m]] as a bit copy for a contiguous tensor of any 4- or 8-byte dtype ([R] or [R, ...]; rows int32 [M]):
+    subgc_gather_rows on the 4-byte word views, which moves words and does no arithmetic on them."""
+    out = torch.empty((rows.numel(),) + tuple(src.shape[1:]), device=src.device, dtype=src.dtype)
+    if out.numel():
+        gather_rows(_words(src.view(-1, 1) if src.dim() == 1 else src), rows, _words(out.view(-1, 1) if out.dim() == 1 else out))
+    return out
+
+
 def gather_rows_keep(src, rows, keep, scale, dst, m_dev=None):
     """dst[m] = src[rows[m]] * keep[m] * scale (keep: uint8 [M, L] or None); src / dst fp32 or bf16."""
     call("subgc_gather_rows_keep", _ptr(src), ld(src), _ptr(rows, torch.int32), _ptr(keep, torch.uint8), ld(keep) if keep is not None else 0, float(scale),

@@ -16,8 +16,14 @@ anywhere on that path.
 `RewardReferences` is the one-time setup (numpy allowed): document frequencies and `ref_len = log(n_img)` are taken over exactly the images
 given -- the upstream "corpus" mode with the training set as the corpus, so `--cached_tokens` needs no file.
 
-Out of scope: the structure-loss and `new_self_critical` variants of later upstream versions, several samples per sub-graph, METEOR and
-SPICE rewards.
+With `sc_samples = n >= 2` (the upstream `train_sample_n` with the `new_self_critical` baseline) the step is ONE pass instead: the decoder
+Function runs n b5 rows, sample-major, and every row draws its own next input word from the logits it has just formed
+(`functions.DecoderFn.forward`, the `sc_onepass` branch), so the rollout and the replay's forward are the same launches and the logits
+`subgc_sc_pick` reads are the logits the criterion differentiates, in every dtype.  There is no greedy half: a sample's baseline is the mean
+score of the other n - 1 samples of its caption row (`SelfCriticalReward.enqueue_loo`, restated by `loo_reward_restatement`).
+
+Out of scope: the structure-loss variants of later upstream versions, the greedy baseline beside several samples, decode rules inside the
+sampling loop, METEOR and SPICE rewards.
 """
 from __future__ import annotations
 
@@ -102,12 +108,61 @@ class SelfCriticalReward:
         if T + 1 > MAX_T:
             raise SubgcError(f"self-critical reward: rollouts of {T} steps are scored as rows of T + 1 = {T + 1} words; the limit is {MAX_T}")
 
-    def _segments(self, S, I, dev):
-        key = (S, I, str(dev))
+    def _segments(self, S, I, dev, n=2, pad=0):
+        """Row boundaries of n blocks of S rows, image i owning S / I rows of every block; `pad` rows behind them form one more segment."""
+        key = (S, I, str(dev), n, pad)
         if key not in self._seg:
             per = S // I
-            self._seg[key] = ops.upload([i * per for i in range(I)] + [S + i * per for i in range(I)] + [2 * S], torch.int32, dev)
+            self._seg[key] = ops.upload([k * S + i * per for k in range(n) for i in range(I)] + [n * S] + ([n * S + pad] if pad else []),
+                                        torch.int32, dev)
         return self._seg[key]
+
+    def _const(self, name, value, dev):
+        key = (name, value, str(dev))
+        if key not in self._seg:
+            self._seg[key] = ops.upload([float(value)], torch.float64, dev)
+        return self._seg[key]
+
+    def enqueue_loo(self, rows, S, d_index, n):
+        """The leave-one-out reward of a one-pass step ("new_self_critical": every sample's baseline is the mean score of the other
+        samples of its caption row).  rows: device int64 [>= S + S % 2, T1], the scored rows as subgc_sc_prepare writes them, of which the
+        first S = n b5 count, sample-major: row k b5 + s is sample k of caption row s, and image i owns the caption rows
+        [i b5 / I, (i + 1) b5 / I) of every sample block; d_index: device int32 [I].
+        -> (reward [S, T1] fp32, mean_reward [] fp32, scores [S] fp64, baseline [S] fp64), on the device, no host read.
+
+        The contract (`loo_reward_restatement` restates it in numpy), every operation a correctly rounded fp64 one, no contraction:
+            s_r          = w_cider * CIDEr_r + w_bleu * BLEU4_r                  as subgc_sc_reward forms it: they are ITS `scores` output
+            tot_s        = ((s_{0,s} + s_{1,s}) + ...) + s_{n-1,s}               over the samples in ascending k
+            baseline_k,s = (tot_s - s_{k,s}) / (n - 1)                           a true division
+            reward[r, t] = float32(s_r - baseline_r)                             for every t < T1
+            mean_reward  = float32(mean of float64(reward[:, 0]))                a statistic; its summation order is not pinned
+        subgc_sc_reward scores an even number of rows, so an odd S scores one padding row more (an all-zero row of the caller's zero
+        half, scored against image d_index[0] in a segment of its own; nothing reads its record).  The header table is closed, so the
+        arithmetic behind `scores` is a handful of elementwise fp64 tensor operations on [n, b5] numbers, each its own launch (which is
+        what keeps a multiply and an add from being contracted): n - 1 adds, a subtract, a divide by a DEVICE scalar (a host scalar
+        would become a multiplication by its reciprocal), a subtract, the cast, and the copy that lays the reward out along t."""
+        n = int(n)
+        if rows.dim() != 2 or rows.dtype != torch.int64 or n < 2 or S % n or rows.size(0) < S + S % 2:
+            raise SubgcError(f"self-critical reward: int64 scored rows [>= {S + S % 2}, T + 1] of {n} >= 2 sample blocks, got {rows.dtype} {tuple(rows.shape)}")
+        b5, T1, I, pad = S // n, rows.size(1), d_index.numel(), S % 2
+        self.check_steps(T1 - 1)
+        if I < 1 or b5 % I:
+            raise SubgcError(f"self-critical reward: {b5} caption rows do not divide over {I} images")
+        dev = rows.device
+        R, segs = S + pad, n * I + pad
+        arena = torch.empty(max(self.scorer.arena_words(R, segs), 2), device=dev, dtype=torch.int32)
+        idx = torch.cat([d_index] * n + ([d_index[:1]] if pad else [])).to(torch.int32)
+        self.scorer.enqueue(rows[:R], self._segments(b5, I, dev, n, pad), segs, idx, None, 0, arena, oracle=False)
+        row_d = self.scorer.views(arena, R, segs)[0]
+        _, _, scores = ops.sc_reward(row_d, R // 2, T1, self.cider_weight, self.bleu_weight)
+        s = scores[:S].view(n, b5)
+        tot = s[0] + s[1]
+        for k in range(2, n):
+            tot = tot + s[k]
+        baseline = (tot.unsqueeze(0) - s) / self._const("n-1", n - 1, dev)
+        r32 = (s - baseline).to(torch.float32).view(S, 1)
+        reward = r32.expand(S, T1).contiguous()
+        return reward, r32.to(torch.float64).mean().to(torch.float32), scores[:S], baseline.view(S)
 
     def enqueue(self, seq2, d_index, rows=None):
         """seq2: device int64 [2S, T], sampled half first; d_index: device int32 [I], the reference image of every batch image, image i
@@ -131,6 +186,41 @@ class SelfCriticalReward:
         self.scorer.enqueue(rows, self._segments(S, I, dev), 2 * I, idx2, None, 0, arena, oracle=False)
         row_d = self.scorer.views(arena, 2 * S, 2 * I)[0]
         return ops.sc_reward(row_d, S, T + 1, self.cider_weight, self.bleu_weight)
+
+
+MAX_SAMPLES = 16
+
+
+def check_samples(sc_samples):
+    """The `sc_samples` / `train_sample_n` option -> int: 1 is the two-pass step with the greedy baseline, 2 .. 16 the one-pass step with the
+    leave-one-out baseline; anything else is refused with the number in the text."""
+    if isinstance(sc_samples, bool) or not isinstance(sc_samples, (int, np.integer)) or not 1 <= int(sc_samples) <= MAX_SAMPLES:
+        raise ValueError(f"sc_samples = {sc_samples!r}: the samples per caption row are an int in 1 .. {MAX_SAMPLES} (1: greedy baseline, two passes; "
+                         f">= 2: leave-one-out baseline, one pass)")
+    return int(sc_samples)
+
+
+def loo_reward_restatement(scores, n):
+    """The contract of `SelfCriticalReward.enqueue_loo` in numpy: scores fp64 [n b5], sample-major -> (reward fp32 [n b5], baseline fp64
+    [n b5], mean_reward float).  Explicit adds in ascending sample order, a true division, one operation per statement."""
+    n = int(n)
+    s = np.asarray(scores, np.float64).reshape(n, -1)
+    if n < 2:
+        raise ValueError(f"loo_reward_restatement: n = {n}; a leave-one-out baseline needs at least 2 samples")
+    tot = s[0] + s[1]
+    for k in range(2, n):
+        tot = tot + s[k]
+    rest = tot[None, :] - s
+    baseline = rest / np.float64(n - 1)
+    reward = (s - baseline).astype(np.float32)
+    return reward.reshape(-1), baseline.reshape(-1), float(reward.astype(np.float64).mean())
+
+
+def onepass_uniforms(model, T, S, dev):
+    """The one-pass step's Philox uniforms [T, S], drawn as `rollout` draws its own: stream SC_STREAM, one more `_sample_calls`."""
+    model.__dict__["_sample_calls"] = model.__dict__.get("_sample_calls", 0) + 1
+    seed = (int(torch.initial_seed()) * 1000003 + model.__dict__["_sample_calls"]) & 0xFFFFFFFFFFFFFFFF
+    return ops.uniform((T, S), seed ^ SC_STREAM, 0, dev)
 
 
 @torch.no_grad()
