@@ -440,6 +440,38 @@ def control_images(model, raw, region_sets, set_off, img_wh, infos, ix_to_word, 
     return preds
 
 
+def proposal_key(image_id):
+    """The sampler key of an image id: a non-negative integer id below 2^43 is its own key; any other id (a file name, say) is keyed by the
+    CRC-32 of its `str`.  A function of the id alone, so `group`, the order of the list and the rank cannot change an image's draw."""
+    if isinstance(image_id, (int, np.integer)) and not isinstance(image_id, bool) and 0 <= int(image_id) < 1 << 43:
+        return int(image_id)
+    import zlib
+    return zlib.crc32(str(image_id).encode("utf-8"))
+
+
+def caption_scene_graphs(model, raw, infos, ix_to_word, proposals, eval_kwargs=None, **scorers):
+    """Captions from raw scene graphs in one device pass, without the reference's sub-graph files: `proposals` (a
+    `subgc.proposals.ProposalSampler`) draws every image's candidate sub-graphs from `raw` (see `ProposalSampler.sample`; the key of an
+    image is `proposal_key` of its id) and the unchanged `caption_images` runs on the sampler's items -- sGPN scores, NMS, the decode
+    and every scorer.  `scorers`: `caption_images`' own keywords (group, shard, grd_pick, consensus, diversity, accuracy, grounding),
+    passed through untouched, as are decode rules and beam search in `eval_kwargs`; with `shard=True` every rank draws the same
+    candidates (the draw is cheap and keyed by the image) and captions its share.  Every entry gains `"proposal"`: {'seed_mask',
+    'node_mask'} (uint64 each), the seed nodes and the final nodes of its captions' sub-graphs in the entry's caption order -- what
+    misc/grd_utils.py:41-42 reads from the mask file.  A model built with sct = 1 is refused: region sets are `control_images`' job."""
+    if getattr(model, "sct", False) or dict(eval_kwargs or {}).get("sct", 0) == 1:
+        raise ValueError("caption_scene_graphs: sampled candidates are ranked and pruned by the sGPN; a model or a call with sct = 1 decodes "
+                         "caller-given region sets (control_images)")
+    if len(infos) != raw["object_fmap"].size(0):
+        raise ValueError("caption_scene_graphs: one `infos` entry per image")
+    drawn = proposals.sample(raw, keys=[proposal_key(info["id"]) for info in infos])
+    preds = caption_images(model, drawn.items, infos, ix_to_word, eval_kwargs, **scorers)
+    t = drawn.table
+    for p, a in zip(preds, t["off"]):
+        rows = int(a) + np.asarray(p["sorted_subgraph_ind"], np.int64)
+        p["proposal"] = {"seed_mask": t["seed_mask"][rows], "node_mask": t["node_mask"][rows]}
+    return preds
+
+
 def grounding_material(entry, boxes, wd_to_lemma, lemma_det_id_dict, det_id_to_det_wd, img_wh=None):
     """misc/grd_utils.py:36-58 for one `predictions` entry of `caption_images(..., return_att=1)`: the sentence ranked
     `entry["grounding"]["subg_index"]`, its words -> lemma -> detection class; for every word that names one, the box of the node
