@@ -30,8 +30,14 @@ __device__ __forceinline__ void subgc_store_act(void* base, int64_t idx, const f
         else *p = o[0];
     }
 }
-// load 4 consecutive bf16 as floats (8-byte aligned)
-__device__ __forceinline__ float4 subgc_load4_bf(const uint16_t* p) {
-    const uint2 q = *reinterpret_cast<const uint2*>(p);
+// 4 packed bf16 as floats
+__device__ __forceinline__ float4 subgc_unpack4(uint2 q) {
     return make_float4(__uint_as_float(q.x << 16), __uint_as_float(q.x & 0xffff0000u), __uint_as_float(q.y << 16), __uint_as_float(q.y & 0xffff0000u));
+}
+// load 4 consecutive bf16 as floats (8-byte aligned)
+__device__ __forceinline__ float4 subgc_load4_bf(const uint16_t* p) { return subgc_unpack4(*reinterpret_cast<const uint2*>(p)); }
+// load 4 consecutive values at element `i` of a source that is bf16 (SRC16) or fp32
+template <bool SRC16>
+__device__ __forceinline__ float4 subgc_load4(const void* base, int64_t i) {
+    return SRC16 ? subgc_load4_bf(static_cast<const uint16_t*>(base) + i) : *reinterpret_cast<const float4*>(static_cast<const float*>(base) + i);
 }

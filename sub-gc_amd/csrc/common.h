@@ -222,12 +222,16 @@ __device__ __forceinline__ void wave_sum_n(float (&v)[N]) {
 // Segment sums of two gather lists at once: sa += fa(ia[j]) for j in [a0, a1), sb += fb(ib[j]) for j in [b0, b1).  Up to four rows of EACH list
 // are requested before any is added (wave-uniform bounds: the skipped loads are scalar branches), additions in list order, so the result is
 // bit-identical to the plain loops -- which waited for every row before asking for the next (degree 2-3 per node: a chain of memory latencies).
-template <class FA, class FB>
+// fa / fb may return a row as it is stored (packed bf16: half the registers while eight rows are in flight); ca / cb then turn it into the
+// float4 that is added.
+struct AsIs { __device__ __forceinline__ float4 operator()(float4 x) const { return x; } };
+template <class FA, class FB, class CA = AsIs, class CB = AsIs>
 __device__ __forceinline__ void gather_pair(const int* __restrict__ ia, int a0, int a1, FA fa, const int* __restrict__ ib, int b0, int b1, FB fb,
-                                            float4& sa, float4& sb) {
+                                            float4& sa, float4& sb, CA ca = CA(), CB cb = CB()) {
     constexpr int U = 4;
     for (int ja = a0, jb = b0; ja < a1 || jb < b1; ja += U, jb += U) {
-        float4 xa[U], xb[U];
+        decltype(fa(0)) xa[U];
+        decltype(fb(0)) xb[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (ja + u < a1) xa[u] = fa(ia[ja + u]);
@@ -235,8 +239,8 @@ __device__ __forceinline__ void gather_pair(const int* __restrict__ ia, int a0, 
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            if (ja + u < a1) { sa.x += xa[u].x; sa.y += xa[u].y; sa.z += xa[u].z; sa.w += xa[u].w; }
-            if (jb + u < b1) { sb.x += xb[u].x; sb.y += xb[u].y; sb.z += xb[u].z; sb.w += xb[u].w; }
+            if (ja + u < a1) { const float4 v = ca(xa[u]); sa.x += v.x; sa.y += v.y; sa.z += v.z; sa.w += v.w; }
+            if (jb + u < b1) { const float4 v = cb(xb[u]); sb.x += v.x; sb.y += v.y; sb.z += v.z; sb.w += v.w; }
         }
     }
 }

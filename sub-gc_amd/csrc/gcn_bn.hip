@@ -1,5 +1,5 @@
 // BatchNorm1d of the Full-GC collection units (graph_conv_unit.py:31-32, nn.BatchNorm1d(dim) on the [rows, L] unit outputs)
-// FUSED into the GCN aggregation kernels that consume it (graph_conv_unit.py:34-36, graph_conv.py:26,33):
+// FUSED into the GCN aggregation kernels that consume it (gcn.hip; graph_conv_unit.py:34-36, graph_conv.py:26,33):
 //   forward   ONE pass over the raw unit output y computes the batch statistics (per-slab shifted sums, merged with Chan's
 //             formula in double), a finishing launch turns them into the per-column triple {mean, gamma * rstd, beta} and updates
 //             the running statistics; the aggregation kernels apply (y - mean) * scale + beta ON LOAD -- the normalised tensor is
@@ -16,29 +16,6 @@
 
 namespace {
 
-constexpr int TC = 128;
-
-template <bool SRC16>
-__device__ __forceinline__ float4 ldsrc(const void* base, int64_t i) {
-    return SRC16 ? subgc_load4_bf(static_cast<const uint16_t*>(base) + i) : *reinterpret_cast<const float4*>(static_cast<const float*>(base) + i);
-}
-struct Aff4 { float4 mu, sc, be; bool on; };
-__device__ __forceinline__ Aff4 load_aff(const float* __restrict__ aff, int L, int col) {
-    Aff4 a;
-    a.on = aff != nullptr;
-    if (a.on) {
-        a.mu = *reinterpret_cast<const float4*>(aff + col);
-        a.sc = *reinterpret_cast<const float4*>(aff + L + col);
-        a.be = *reinterpret_cast<const float4*>(aff + 2 * L + col);
-    }
-    return a;
-}
-__device__ __forceinline__ float4 apply_aff(const Aff4& a, float4 x) {
-    if (!a.on) return x;
-    return make_float4((x.x - a.mu.x) * a.sc.x + a.be.x, (x.y - a.mu.y) * a.sc.y + a.be.y, (x.z - a.mu.z) * a.sc.z + a.be.z,
-                       (x.w - a.mu.w) * a.sc.w + a.be.w);
-}
-
 // ------------------------------------------------------------------ statistics
 // grid (C/256, slabs): part[slab][{sum (x - p), sum (x - p)^2, p}][C], p = the slab's first row (shifted-data sums)
 template <bool SRC16>
@@ -48,12 +25,12 @@ __device__ __forceinline__ void bn_stats_body(const void* __restrict__ X, int M,
     const int r0 = blockIdx.y * rpb, r1 = min(M, r0 + rpb);
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f), q = s, p = s;
     if (col < C) {
-        p = ldsrc<SRC16>(X, (int64_t)r0 * C + col);
+        p = subgc_load4<SRC16>(X, (int64_t)r0 * C + col);
         int r = r0 + w;
         for (; r + 12 < r1; r += 16) {
             float4 x[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) x[k] = ldsrc<SRC16>(X, (int64_t)(r + 4 * k) * C + col);
+            for (int k = 0; k < 4; ++k) x[k] = subgc_load4<SRC16>(X, (int64_t)(r + 4 * k) * C + col);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const float d0 = x[k].x - p.x, d1 = x[k].y - p.y, d2 = x[k].z - p.z, d3 = x[k].w - p.w;
@@ -62,7 +39,7 @@ __device__ __forceinline__ void bn_stats_body(const void* __restrict__ X, int M,
             }
         }
         for (; r < r1; r += 4) {
-            const float4 x = ldsrc<SRC16>(X, (int64_t)r * C + col);
+            const float4 x = subgc_load4<SRC16>(X, (int64_t)r * C + col);
             const float d0 = x.x - p.x, d1 = x.y - p.y, d2 = x.z - p.z, d3 = x.w - p.w;
             s.x += d0; s.y += d1; s.z += d2; s.w += d3;
             q.x += d0 * d0; q.y += d1 * d1; q.z += d2 * d2; q.w += d3 * d3;
@@ -184,200 +161,6 @@ __global__ __launch_bounds__(256) void bn_eval_aff_kernel(int C, const float* __
     if (rstd_out) rstd_out[c] = rs;
 }
 
-// ------------------------------------------------------------------ nodes <- relations with the unit outputs normalised on load
-template <bool SRC16>
-__global__ __launch_bounds__(256) void gcn_nodes_fwd_bn_kernel(const void* __restrict__ F0, const void* __restrict__ F1,
-                                                               const float* __restrict__ aff0, const float* __restrict__ aff1,
-                                                               const int32_t* __restrict__ ptr, const int32_t* __restrict__ edges,
-                                                               const float* __restrict__ skip, float* __restrict__ Xout,
-                                                               uint16_t* __restrict__ Xout16, uint8_t* __restrict__ act, int B, int N, int K, int L) {
-    extern __shared__ int sm_i[];
-    int* ps = sm_i; int* po = ps + (N + 1); int* es = po + (N + 1); int* eo = es + K;
-    const int b = blockIdx.y;
-    for (int i = threadIdx.x; i <= N; i += blockDim.x) {
-        ps[i] = ptr[((int64_t)0 * B + b) * (N + 1) + i];
-        po[i] = ptr[((int64_t)1 * B + b) * (N + 1) + i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-        es[i] = edges[((int64_t)0 * B + b) * K + i];
-        eo[i] = edges[((int64_t)1 * B + b) * K + i];
-    }
-    __syncthreads();
-    const int col = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (col >= L) return;
-    const Aff4 A0 = load_aff(aff0, L, col), A1 = load_aff(aff1, L, col);
-    const int64_t base = (int64_t)b * K * L + col;
-    for (int n = blockIdx.z; n < N; n += gridDim.z) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), c = a;
-        const int s0 = ps[n], s1 = ps[n + 1], o0 = po[n], o1 = po[n + 1];
-        gather_pair(es, s0, s1, [&](int e) { return apply_aff(A0, ldsrc<SRC16>(F0, base + (int64_t)e * L)); },
-                    eo, o0, o1, [&](int e) { return apply_aff(A1, ldsrc<SRC16>(F1, base + (int64_t)e * L)); }, a, c);
-        const float da = (float)(s1 - s0) + 1e-7f, dc = (float)(o1 - o0) + 1e-7f;
-        const float av[4] = {a.x / da, a.y / da, a.z / da, a.w / da}, cv[4] = {c.x / dc, c.y / dc, c.z / dc, c.w / dc};
-        const int64_t o = ((int64_t)b * N + n) * L + col;
-        float4 sk = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (skip) sk = *reinterpret_cast<const float4*>(skip + o);
-        const float skv[4] = {sk.x, sk.y, sk.z, sk.w};
-        float v[4];
-        uint32_t bits = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            bits |= (uint32_t)((av[e] > 0.f ? 1 : 0) | (cv[e] > 0.f ? 2 : 0)) << (8 * e);
-            v[e] = (fmaxf(av[e], 0.f) + fmaxf(cv[e], 0.f)) / 2.f;
-            if (skip) v[e] += skv[e];
-        }
-        *reinterpret_cast<float4*>(Xout + o) = make_float4(v[0], v[1], v[2], v[3]);
-        if (Xout16) *reinterpret_cast<uint2*>(Xout16 + o) = subgc_pack4(v[0], v[1], v[2], v[3]);
-        if (act) *reinterpret_cast<uint32_t*>(act + o) = bits;
-    }
-}
-
-// ------------------------------------------------------------------ relations <- nodes (node tiles staged in LDS, normalised while staging)
-template <bool SRC16>
-__global__ __launch_bounds__(256) void gcn_edges_fwd_bn_kernel(const void* __restrict__ F2, const void* __restrict__ F3,
-                                                               const float* __restrict__ aff2, const float* __restrict__ aff3,
-                                                               const int64_t* __restrict__ rel_ind, const float* __restrict__ skip,
-                                                               float* __restrict__ Pout, uint16_t* __restrict__ Pout16, int B, int N, int K, int L, int vec) {
-    extern __shared__ __attribute__((aligned(16))) float sm_f[];
-    float* t2 = sm_f;
-    float* t3 = sm_f + (size_t)N * TC;
-    int* ns = reinterpret_cast<int*>(t3 + (size_t)N * TC);
-    int* no = ns + K;
-    const int b = blockIdx.y, c0 = blockIdx.x * TC;
-    const float cdiv1 = 1.f + 1e-7f;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        int64_t s = rel_ind[((int64_t)b * K + k) * 2 + 0], o = rel_ind[((int64_t)b * K + k) * 2 + 1];
-        ns[k] = (int)(s < 0 ? 0 : (s >= N ? N - 1 : s));
-        no[k] = (int)(o < 0 ? 0 : (o >= N ? N - 1 : o));
-    }
-    const int items = N * (TC / 4);
-    for (int i0 = threadIdx.x; i0 < items; i0 += 4 * blockDim.x) {         // four node-row quads requested before the first is staged
-        float4 a[4], c[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = i0 + u * blockDim.x;
-            a[u] = make_float4(0.f, 0.f, 0.f, 0.f); c[u] = a[u];
-            if (i < items) {
-                const int n = i / (TC / 4), c4 = (i % (TC / 4)) * 4;
-                if (c0 + c4 < L) {                                        // L % 4 == 0: a float4 is all in or all out
-                    const int64_t g = ((int64_t)b * N + n) * L + c0 + c4;
-                    a[u] = ldsrc<SRC16>(F2, g);
-                    c[u] = ldsrc<SRC16>(F3, g);
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = i0 + u * blockDim.x;
-            if (i < items) {
-                const int n = i / (TC / 4), c4 = (i % (TC / 4)) * 4;
-                float4 x = make_float4(0.f, 0.f, 0.f, 0.f), y = x;
-                if (c0 + c4 < L) {
-                    x = apply_aff(load_aff(aff2, L, c0 + c4), a[u]);
-                    y = apply_aff(load_aff(aff3, L, c0 + c4), c[u]);
-                }
-                x.x = fmaxf(x.x / cdiv1, 0.f); x.y = fmaxf(x.y / cdiv1, 0.f); x.z = fmaxf(x.z / cdiv1, 0.f); x.w = fmaxf(x.w / cdiv1, 0.f);
-                y.x = fmaxf(y.x / cdiv1, 0.f); y.y = fmaxf(y.y / cdiv1, 0.f); y.z = fmaxf(y.z / cdiv1, 0.f); y.w = fmaxf(y.w / cdiv1, 0.f);
-                *reinterpret_cast<float4*>(t2 + n * TC + c4) = x;
-                *reinterpret_cast<float4*>(t3 + n * TC + c4) = y;
-            }
-        }
-    }
-    __syncthreads();
-    if (vec) {                                                             // 8 relation streams x 32 lanes x 4 columns: 16-byte LDS reads and stores
-        const int cl4 = (threadIdx.x & 31) * 4, st = threadIdx.x >> 5;
-        if (c0 + cl4 >= L) return;
-        for (int k0 = st; k0 < K; k0 += 32) {
-            float4 v[4], sk[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + 8 * u;
-                if (k < K) {
-                    const float4 x = *reinterpret_cast<const float4*>(t2 + ns[k] * TC + cl4), y = *reinterpret_cast<const float4*>(t3 + no[k] * TC + cl4);
-                    v[u] = make_float4((x.x + y.x) / 2.f, (x.y + y.y) / 2.f, (x.z + y.z) / 2.f, (x.w + y.w) / 2.f);
-                    if (skip) sk[u] = *reinterpret_cast<const float4*>(skip + ((int64_t)b * K + k) * L + c0 + cl4);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + 8 * u;
-                if (k < K) {
-                    float4 r = v[u];
-                    if (skip) { r.x += sk[u].x; r.y += sk[u].y; r.z += sk[u].z; r.w += sk[u].w; }
-                    const int64_t o = ((int64_t)b * K + k) * L + c0 + cl4;
-                    *reinterpret_cast<float4*>(Pout + o) = r;
-                    if (Pout16) *reinterpret_cast<uint2*>(Pout16 + o) = subgc_pack4(r.x, r.y, r.z, r.w);
-                }
-            }
-        }
-        return;
-    }
-    const int cl = threadIdx.x & (TC - 1), half = threadIdx.x >> 7;
-    const int col = c0 + cl;
-    if (col >= L) return;
-    for (int k0 = half; k0 < K; k0 += 8) {                                 // four relations per round: LDS reads and skip loads in flight together
-        float v[4], sk[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = k0 + 2 * u;
-            if (k < K) {
-                v[u] = (t2[ns[k] * TC + cl] + t3[no[k] * TC + cl]) / 2.f;
-                sk[u] = skip ? skip[((int64_t)b * K + k) * L + col] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = k0 + 2 * u;
-            if (k < K) {
-                const int64_t o = ((int64_t)b * K + k) * L + col;
-                const float r = skip ? v[u] + sk[u] : v[u];
-                Pout[o] = r;
-                if (Pout16) Pout16[o] = (uint16_t)subgc_f2bf(r);
-            }
-        }
-    }
-}
-
-template <bool SRC16>
-__global__ __launch_bounds__(256) void gcn_edges_bwd_bn_kernel(const float* __restrict__ dP, const void* __restrict__ F2,
-                                                               const void* __restrict__ F3, const float* __restrict__ aff2,
-                                                               const float* __restrict__ aff3, const int32_t* __restrict__ ptr,
-                                                               const int32_t* __restrict__ edges, void* __restrict__ dF2,
-                                                               void* __restrict__ dF3, int B, int N, int K, int L, int o16) {
-    extern __shared__ int sm_i[];
-    int* ps = sm_i; int* po = ps + (N + 1); int* es = po + (N + 1); int* eo = es + K;
-    const int b = blockIdx.y;
-    for (int i = threadIdx.x; i <= N; i += blockDim.x) {
-        ps[i] = ptr[((int64_t)0 * B + b) * (N + 1) + i];
-        po[i] = ptr[((int64_t)1 * B + b) * (N + 1) + i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-        es[i] = edges[((int64_t)0 * B + b) * K + i];
-        eo[i] = edges[((int64_t)1 * B + b) * K + i];
-    }
-    __syncthreads();
-    const int col = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (col >= L) return;
-    const Aff4 A2 = load_aff(aff2, L, col), A3 = load_aff(aff3, L, col);
-    const float cdiv1 = 1.f + 1e-7f;
-    const float* dp = dP + (int64_t)b * K * L + col;
-    for (int n = blockIdx.z; n < N; n += gridDim.z) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), c = a;
-        const int64_t o = ((int64_t)b * N + n) * L + col;
-        const float4 f2 = apply_aff(A2, ldsrc<SRC16>(F2, o)), f3 = apply_aff(A3, ldsrc<SRC16>(F3, o));
-        auto row = [&](int e) { return *reinterpret_cast<const float4*>(dp + (int64_t)e * L); };
-        gather_pair(es, ps[n], ps[n + 1], row, eo, po[n], po[n + 1], row, a, c);
-        float4 r2, r3;
-        r2.x = (f2.x / cdiv1 > 0.f) ? a.x * 0.5f / cdiv1 : 0.f; r2.y = (f2.y / cdiv1 > 0.f) ? a.y * 0.5f / cdiv1 : 0.f;
-        r2.z = (f2.z / cdiv1 > 0.f) ? a.z * 0.5f / cdiv1 : 0.f; r2.w = (f2.w / cdiv1 > 0.f) ? a.w * 0.5f / cdiv1 : 0.f;
-        r3.x = (f3.x / cdiv1 > 0.f) ? c.x * 0.5f / cdiv1 : 0.f; r3.y = (f3.y / cdiv1 > 0.f) ? c.y * 0.5f / cdiv1 : 0.f;
-        r3.z = (f3.z / cdiv1 > 0.f) ? c.z * 0.5f / cdiv1 : 0.f; r3.w = (f3.w / cdiv1 > 0.f) ? c.w * 0.5f / cdiv1 : 0.f;
-        const float o2[4] = {r2.x, r2.y, r2.z, r2.w}, o3[4] = {r3.x, r3.y, r3.z, r3.w};
-        subgc_store_act<4>(dF2, o, o2, o16);
-        subgc_store_act<4>(dF3, o, o3, o16);
-    }
-}
-
 // ------------------------------------------------------------------ BatchNorm backward
 // grid (C/256, slabs): part[slab][{sum dy * xhat, sum dy}][C]
 template <bool SRC16>
@@ -393,14 +176,14 @@ __device__ __forceinline__ void bn_bwd_reduce2_body(const float* __restrict__ dY
         int r = r0 + w;
         for (; r + 4 < r1; r += 8) {
             const float4 d0 = *reinterpret_cast<const float4*>(dY + (int64_t)r * C + col), d1 = *reinterpret_cast<const float4*>(dY + (int64_t)(r + 4) * C + col);
-            const float4 x0 = ldsrc<SRC16>(X, (int64_t)r * C + col), x1 = ldsrc<SRC16>(X, (int64_t)(r + 4) * C + col);
+            const float4 x0 = subgc_load4<SRC16>(X, (int64_t)r * C + col), x1 = subgc_load4<SRC16>(X, (int64_t)(r + 4) * C + col);
             ab.x += d0.x + d1.x; ab.y += d0.y + d1.y; ab.z += d0.z + d1.z; ab.w += d0.w + d1.w;
             ag.x += d0.x * (x0.x - mu.x) * rs.x + d1.x * (x1.x - mu.x) * rs.x; ag.y += d0.y * (x0.y - mu.y) * rs.y + d1.y * (x1.y - mu.y) * rs.y;
             ag.z += d0.z * (x0.z - mu.z) * rs.z + d1.z * (x1.z - mu.z) * rs.z; ag.w += d0.w * (x0.w - mu.w) * rs.w + d1.w * (x1.w - mu.w) * rs.w;
         }
         for (; r < r1; r += 4) {
             const float4 dy = *reinterpret_cast<const float4*>(dY + (int64_t)r * C + col);
-            const float4 x = ldsrc<SRC16>(X, (int64_t)r * C + col);
+            const float4 x = subgc_load4<SRC16>(X, (int64_t)r * C + col);
             ab.x += dy.x; ab.y += dy.y; ab.z += dy.z; ab.w += dy.w;
             ag.x += dy.x * (x.x - mu.x) * rs.x; ag.y += dy.y * (x.y - mu.y) * rs.y;
             ag.z += dy.z * (x.z - mu.z) * rs.z; ag.w += dy.w * (x.w - mu.w) * rs.w;
@@ -478,14 +261,14 @@ __device__ __forceinline__ void bn_bwd_apply2_body(const float* __restrict__ dY,
         for (int u = 0; u < 4; ++u) {
             const int64_t o = (int64_t)(r + 4 * u) * C + col;
             dy[u] = *reinterpret_cast<const float4*>(dY + o);
-            x[u] = ldsrc<SRC16>(X, o);
+            x[u] = subgc_load4<SRC16>(X, o);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) one((int64_t)(r + 4 * u) * C + col, dy[u], x[u]);
     }
     for (; r < r1; r += 4) {
         const int64_t o = (int64_t)r * C + col;
-        one(o, *reinterpret_cast<const float4*>(dY + o), ldsrc<SRC16>(X, o));
+        one(o, *reinterpret_cast<const float4*>(dY + o), subgc_load4<SRC16>(X, o));
     }
 }
 
@@ -496,7 +279,6 @@ inline int stat_rows_per_block(int M, int C) {
     const int slabs = std::max(1, 512 / col_groups);
     return std::max(16, (M + slabs - 1) / slabs);
 }
-inline int raise_lds(const void* fn, size_t bytes, const char* what) { return subgc::raise_lds_cached(fn, bytes, what); }
 
 template <bool SRC16>
 __global__ __launch_bounds__(256) void bn_bwd_reduce2_kernel(const float* __restrict__ dY, const void* __restrict__ X, int M, int C,
@@ -634,58 +416,4 @@ SUBGC_API int subgc_bn_bwd_fused_pair(const float* dY0, const float* dY1, const 
     else { if (dx_bf16) SUBGC_BN_APPLY(false, true); else SUBGC_BN_APPLY(false, false); }
 #undef SUBGC_BN_APPLY
     return subgc::check_launch("subgc_bn_bwd_fused_pair");
-}
-
-SUBGC_API int subgc_gcn_nodes_fwd_bn(const void* F0, const void* F1, int f_bf16, const float* aff0, const float* aff1, const int32_t* ptr,
-                                     const int32_t* edges, const float* skip, float* Xout, uint16_t* Xout16, uint8_t* act, int B, int N, int K,
-                                     int L, void* stream) {
-    SUBGC_REQUIRE(B >= 0 && N > 0 && K > 0 && L > 0 && L % 4 == 0, "gcn_nodes_fwd_bn: bad sizes (L must be a multiple of 4)");
-    if (B == 0) return SUBGC_OK;
-    SUBGC_REQUIRE(F0 && F1 && ptr && edges && Xout, "gcn_nodes_fwd_bn: null pointer");
-    SUBGC_REQUIRE((f_bf16 ? (al8(F0) && al8(F1)) : (al16(F0) && al16(F1))) && al16(skip) && al16(Xout) && al8(Xout16) && al16(aff0) && al16(aff1) &&
-                      (reinterpret_cast<uintptr_t>(act) & 3) == 0, "gcn_nodes_fwd_bn: misaligned pointer");
-    hipStream_t s = (hipStream_t)stream;
-    subgc::ProfScope prof(SUBGC_FAM_GCN, s, (f_bf16 ? 2.0 : 4.0) * B * L * 2.0 * K + 4.0 * B * L * (skip ? 2.0 : 1.0) * N);
-    const size_t lds = sizeof(int) * (2 * (N + 1) + 2 * K);
-    const dim3 g((L / 4 + 255) / 256, B, subgc::gcn_zsplit((L / 4 + 255) / 256, B, N));
-    if (f_bf16) hipLaunchKernelGGL((gcn_nodes_fwd_bn_kernel<true>), g, dim3(256), lds, s, F0, F1, aff0, aff1, ptr, edges, skip, Xout, Xout16, act, B, N, K, L);
-    else hipLaunchKernelGGL((gcn_nodes_fwd_bn_kernel<false>), g, dim3(256), lds, s, F0, F1, aff0, aff1, ptr, edges, skip, Xout, Xout16, act, B, N, K, L);
-    return subgc::check_launch("subgc_gcn_nodes_fwd_bn");
-}
-
-SUBGC_API int subgc_gcn_edges_fwd_bn(const void* F2, const void* F3, int f_bf16, const float* aff2, const float* aff3, const int64_t* rel_ind,
-                                     const float* skip, float* Pout, uint16_t* Pout16, int B, int N, int K, int L, void* stream) {
-    SUBGC_REQUIRE(B >= 0 && N > 0 && K > 0 && L > 0 && L % 4 == 0, "gcn_edges_fwd_bn: bad sizes (L must be a multiple of 4)");
-    if (B == 0) return SUBGC_OK;
-    SUBGC_REQUIRE(F2 && F3 && rel_ind && Pout, "gcn_edges_fwd_bn: null pointer");
-    SUBGC_DEBUG_RANGE(rel_ind, 8, (int64_t)B * K, 2, 2, 0, N - 1, -1, "gcn_edges_fwd_bn: rel_ind", stream);
-    SUBGC_REQUIRE((f_bf16 ? (al8(F2) && al8(F3)) : (al16(F2) && al16(F3))) && al16(aff2) && al16(aff3), "gcn_edges_fwd_bn: misaligned pointer");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t lds = sizeof(float) * 2 * (size_t)N * TC + sizeof(int) * 2 * K;
-    int rc = f_bf16 ? raise_lds((const void*)gcn_edges_fwd_bn_kernel<true>, lds, "gcn_edges_fwd_bn")
-                    : raise_lds((const void*)gcn_edges_fwd_bn_kernel<false>, lds, "gcn_edges_fwd_bn");
-    if (rc) return rc;
-    subgc::ProfScope prof(SUBGC_FAM_GCN, s, (f_bf16 ? 2.0 : 4.0) * B * L * 2.0 * N + 4.0 * B * L * (skip ? 2.0 : 1.0) * K);
-    const dim3 g((L + TC - 1) / TC, B);
-    const int vec = al16(Pout) && al16(skip) && al8(Pout16);
-    if (f_bf16) hipLaunchKernelGGL((gcn_edges_fwd_bn_kernel<true>), g, dim3(256), lds, s, F2, F3, aff2, aff3, rel_ind, skip, Pout, Pout16, B, N, K, L, vec);
-    else hipLaunchKernelGGL((gcn_edges_fwd_bn_kernel<false>), g, dim3(256), lds, s, F2, F3, aff2, aff3, rel_ind, skip, Pout, Pout16, B, N, K, L, vec);
-    return subgc::check_launch("subgc_gcn_edges_fwd_bn");
-}
-
-SUBGC_API int subgc_gcn_edges_bwd_bn(const float* dP, const void* F2, const void* F3, int f_bf16, const float* aff2, const float* aff3,
-                                     const int32_t* ptr, const int32_t* edges, void* dF2, void* dF3, int out_bf16, int B, int N, int K, int L,
-                                     void* stream) {
-    SUBGC_REQUIRE(B >= 0 && N > 0 && K > 0 && L > 0 && L % 4 == 0, "gcn_edges_bwd_bn: bad sizes (L must be a multiple of 4)");
-    if (B == 0) return SUBGC_OK;
-    SUBGC_REQUIRE(dP && F2 && F3 && ptr && edges && dF2 && dF3, "gcn_edges_bwd_bn: null pointer");
-    SUBGC_REQUIRE(al16(dP) && (f_bf16 ? (al8(F2) && al8(F3)) : (al16(F2) && al16(F3))) && (out_bf16 ? (al8(dF2) && al8(dF3)) : (al16(dF2) && al16(dF3))) &&
-                      al16(aff2) && al16(aff3), "gcn_edges_bwd_bn: misaligned pointer");
-    hipStream_t s = (hipStream_t)stream;
-    subgc::ProfScope prof(SUBGC_FAM_GCN, s, 4.0 * B * L * (2.0 * K + 2.0 * N) + (f_bf16 ? 2.0 : 4.0) * B * L * 2.0 * N);
-    const size_t lds = sizeof(int) * (2 * (N + 1) + 2 * K);
-    const dim3 g((L / 4 + 255) / 256, B, subgc::gcn_zsplit((L / 4 + 255) / 256, B, N));
-    if (f_bf16) hipLaunchKernelGGL((gcn_edges_bwd_bn_kernel<true>), g, dim3(256), lds, s, dP, F2, F3, aff2, aff3, ptr, edges, dF2, dF3, B, N, K, L, out_bf16);
-    else hipLaunchKernelGGL((gcn_edges_bwd_bn_kernel<false>), g, dim3(256), lds, s, dP, F2, F3, aff2, aff3, ptr, edges, dF2, dF3, B, N, K, L, out_bf16);
-    return subgc::check_launch("subgc_gcn_edges_bwd_bn");
 }

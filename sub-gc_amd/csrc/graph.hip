@@ -1,12 +1,11 @@
-// Scene-graph kernels: class arg-max, CSR build, GCN neighbour aggregation (fwd + bwd), BatchNorm.
-// All are HBM-bound streaming kernels: threads run along the feature dimension L (coalesced
-// 256-float rows), indices live in LDS, node tiles are LDS-staged where rows are re-used.
+// Scene-graph kernels: class arg-max, CSR build, the unfused BatchNorm, the aggregate-first pair (the GCN neighbour aggregation
+// itself: gcn.hip).  All are HBM-bound streaming kernels: threads run along the feature dimension (coalesced rows), indices live in LDS.
 //
 // Reference op sites: AttModel.py:376,383,385 (argmax); gcn_backbone.py:55-67 (make_map, replaced
-// by CSR); graph_conv_unit.py:28-36 (bmm + normalise + ReLU, BatchNorm); graph_conv.py:24-33
-// (average of the two roles); gcn_backbone.py:43-47 (residual).
+// by CSR); graph_conv_unit.py:28-36 (BatchNorm).
 #include "common.h"
 #include "bf16_util.h"
+#include "gcn_lists.h"
 
 #include <algorithm>
 
@@ -69,357 +68,6 @@ __global__ __launch_bounds__(256) void csr_build_kernel(const int64_t* __restric
         int pos = start[n];
         for (int k = 0; k < K; ++k)
             if (node_of[k] == n) e[pos++] = k;
-    }
-}
-
-// ------------------------------------------------------------------ nodes <- relations
-// grid (L/256, B); thread = one feature column; CSR lists of the image in LDS.
-__global__ __launch_bounds__(256) void gcn_nodes_fwd_kernel(const float* __restrict__ F0, const float* __restrict__ F1,
-                                                            const int32_t* __restrict__ ptr,
-                                                            const int32_t* __restrict__ edges,
-                                                            const float* __restrict__ skip, float* __restrict__ Xout,
-                                                            uint8_t* __restrict__ act, int B, int N, int K, int L) {
-    extern __shared__ int sm_i[];
-    int* ps = sm_i;                 // [N+1] subject ptr
-    int* po = ps + (N + 1);         // [N+1] object ptr
-    int* es = po + (N + 1);         // [K]
-    int* eo = es + K;               // [K]
-    const int b = blockIdx.y;
-    for (int i = threadIdx.x; i <= N; i += blockDim.x) {
-        ps[i] = ptr[((int64_t)0 * B + b) * (N + 1) + i];
-        po[i] = ptr[((int64_t)1 * B + b) * (N + 1) + i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-        es[i] = edges[((int64_t)0 * B + b) * K + i];
-        eo[i] = edges[((int64_t)1 * B + b) * K + i];
-    }
-    __syncthreads();
-    const int col = blockIdx.x * 256 + threadIdx.x;
-    if (col >= L) return;
-    const float* f0 = F0 + (int64_t)b * K * L + col;
-    const float* f1 = F1 + (int64_t)b * K * L + col;
-    for (int n = blockIdx.z; n < N; n += gridDim.z) {           // node chunks over gridDim.z: shorter dependent chains, 4x the loads in flight
-        float a = 0.f, c = 0.f;
-        const int s0 = ps[n], s1 = ps[n + 1], o0 = po[n], o1 = po[n + 1];
-        for (int j = s0; j < s1; ++j) a += f0[(int64_t)es[j] * L];
-        for (int j = o0; j < o1; ++j) c += f1[(int64_t)eo[j] * L];
-        a = a / ((float)(s1 - s0) + 1e-7f);
-        c = c / ((float)(o1 - o0) + 1e-7f);
-        const uint8_t bits = (a > 0.f ? 1 : 0) | (c > 0.f ? 2 : 0);
-        float v = (fmaxf(a, 0.f) + fmaxf(c, 0.f)) / 2.f;
-        const int64_t o = ((int64_t)b * N + n) * L + col;
-        if (skip) v += skip[o];
-        Xout[o] = v;
-        if (act) act[o] = bits;
-    }
-}
-
-// float4 form of the same kernel (L % 4 == 0, 16-byte aligned rows): a thread owns four adjacent columns, so a wave reads 1 KB
-// of a relation row per instruction instead of 256 B (the scalar form ran at 2.3 TB/s on Full-GC's 65 x 1024 relation rows);
-// every element is summed in the same order as before (bit-identical results)
-__global__ __launch_bounds__(256) void gcn_nodes_fwd_vec_kernel(const float* __restrict__ F0, const float* __restrict__ F1,
-                                                                const int32_t* __restrict__ ptr, const int32_t* __restrict__ edges,
-                                                                const float* __restrict__ skip, float* __restrict__ Xout,
-                                                                uint8_t* __restrict__ act, int B, int N, int K, int L) {
-    extern __shared__ int sm_i[];
-    int* ps = sm_i; int* po = ps + (N + 1); int* es = po + (N + 1); int* eo = es + K;
-    const int b = blockIdx.y;
-    for (int i = threadIdx.x; i <= N; i += blockDim.x) {
-        ps[i] = ptr[((int64_t)0 * B + b) * (N + 1) + i];
-        po[i] = ptr[((int64_t)1 * B + b) * (N + 1) + i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-        es[i] = edges[((int64_t)0 * B + b) * K + i];
-        eo[i] = edges[((int64_t)1 * B + b) * K + i];
-    }
-    __syncthreads();
-    const int col = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (col >= L) return;
-    const float* f0 = F0 + (int64_t)b * K * L + col;
-    const float* f1 = F1 + (int64_t)b * K * L + col;
-    for (int n = blockIdx.z; n < N; n += gridDim.z) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), c = a;
-        const int s0 = ps[n], s1 = ps[n + 1], o0 = po[n], o1 = po[n + 1];
-        gather_pair(es, s0, s1, [&](int e) { return *reinterpret_cast<const float4*>(f0 + (int64_t)e * L); },
-                    eo, o0, o1, [&](int e) { return *reinterpret_cast<const float4*>(f1 + (int64_t)e * L); }, a, c);
-        const float da = (float)(s1 - s0) + 1e-7f, dc = (float)(o1 - o0) + 1e-7f;
-        float av[4] = {a.x / da, a.y / da, a.z / da, a.w / da}, cv[4] = {c.x / dc, c.y / dc, c.z / dc, c.w / dc};
-        const int64_t o = ((int64_t)b * N + n) * L + col;
-        float4 sk = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (skip) sk = *reinterpret_cast<const float4*>(skip + o);
-        const float skv[4] = {sk.x, sk.y, sk.z, sk.w};
-        float v[4];
-        uint32_t bits = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            bits |= (uint32_t)((av[e] > 0.f ? 1 : 0) | (cv[e] > 0.f ? 2 : 0)) << (8 * e);
-            v[e] = (fmaxf(av[e], 0.f) + fmaxf(cv[e], 0.f)) / 2.f;
-            if (skip) v[e] += skv[e];
-        }
-        *reinterpret_cast<float4*>(Xout + o) = make_float4(v[0], v[1], v[2], v[3]);
-        if (act) *reinterpret_cast<uint32_t*>(act + o) = bits;
-    }
-}
-
-// dF0[b,k,:] = 1/2 [bit0](b,s_k,:) dX[b,s_k,:] / (cnt_s[s_k] + 1e-7);  dF1 likewise with o_k / bit1
-__global__ __launch_bounds__(256) void gcn_nodes_bwd_kernel(const float* __restrict__ dX, const uint8_t* __restrict__ act,
-                                                            const int64_t* __restrict__ rel_ind,
-                                                            const int32_t* __restrict__ ptr, float* __restrict__ dF0,
-                                                            float* __restrict__ dF1, int B, int N, int K, int L) {
-    extern __shared__ int sm_i[];
-    int* ns = sm_i;            // [K] subject node of k
-    int* no = ns + K;          // [K] object node of k
-    float* ds = reinterpret_cast<float*>(no + K);   // [N] cnt_s + 1e-7 denominators
-    float* dn_o = ds + N;
-    const int b = blockIdx.y;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        int64_t s = rel_ind[((int64_t)b * K + k) * 2 + 0], o = rel_ind[((int64_t)b * K + k) * 2 + 1];
-        ns[k] = (int)(s < 0 ? 0 : (s >= N ? N - 1 : s));
-        no[k] = (int)(o < 0 ? 0 : (o >= N ? N - 1 : o));
-    }
-    for (int n = threadIdx.x; n < N; n += blockDim.x) {
-        const int32_t* p0 = ptr + ((int64_t)0 * B + b) * (N + 1);
-        const int32_t* p1 = ptr + ((int64_t)1 * B + b) * (N + 1);
-        ds[n] = (float)(p0[n + 1] - p0[n]) + 1e-7f;
-        dn_o[n] = (float)(p1[n + 1] - p1[n]) + 1e-7f;
-    }
-    __syncthreads();
-    const int col = blockIdx.x * 256 + threadIdx.x;
-    if (col >= L) return;
-    for (int k = blockIdx.z; k < K; k += gridDim.z) {
-        const int s = ns[k], o = no[k];
-        const int64_t is = ((int64_t)b * N + s) * L + col, io = ((int64_t)b * N + o) * L + col;
-        const float gs = (act[is] & 1) ? dX[is] * 0.5f / ds[s] : 0.f;
-        const float go = (act[io] & 2) ? dX[io] * 0.5f / dn_o[o] : 0.f;
-        const int64_t ok = ((int64_t)b * K + k) * L + col;
-        dF0[ok] = gs;
-        dF1[ok] = go;
-    }
-}
-
-// o16: dF0 / dF1 are bf16 (the unit outputs they are gradients of were bf16 GEMM results: compute_dtype = bf16 without BatchNorm)
-__global__ __launch_bounds__(256) void gcn_nodes_bwd_vec_kernel(const float* __restrict__ dX, const uint8_t* __restrict__ act,
-                                                                const int64_t* __restrict__ rel_ind, const int32_t* __restrict__ ptr,
-                                                                void* __restrict__ dF0, void* __restrict__ dF1, int B, int N, int K, int L, int o16) {
-    extern __shared__ int sm_i[];
-    int* ns = sm_i; int* no = ns + K;
-    float* ds = reinterpret_cast<float*>(no + K); float* dn_o = ds + N;
-    const int b = blockIdx.y;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        int64_t s = rel_ind[((int64_t)b * K + k) * 2 + 0], o = rel_ind[((int64_t)b * K + k) * 2 + 1];
-        ns[k] = (int)(s < 0 ? 0 : (s >= N ? N - 1 : s));
-        no[k] = (int)(o < 0 ? 0 : (o >= N ? N - 1 : o));
-    }
-    for (int n = threadIdx.x; n < N; n += blockDim.x) {
-        const int32_t* p0 = ptr + ((int64_t)0 * B + b) * (N + 1);
-        const int32_t* p1 = ptr + ((int64_t)1 * B + b) * (N + 1);
-        ds[n] = (float)(p0[n + 1] - p0[n]) + 1e-7f;
-        dn_o[n] = (float)(p1[n + 1] - p1[n]) + 1e-7f;
-    }
-    __syncthreads();
-    const int col = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (col >= L) return;
-    const int kz = gridDim.z;
-    for (int k0 = blockIdx.z; k0 < K; k0 += 4 * kz) {                      // four relations' node rows requested before the first is used
-        int sn[4], on[4];
-        uint32_t as[4], ao[4];
-        float4 xs[4], xo[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = k0 + u * kz;
-            if (k < K) {
-                sn[u] = ns[k]; on[u] = no[k];
-                const int64_t is = ((int64_t)b * N + sn[u]) * L + col, io = ((int64_t)b * N + on[u]) * L + col;
-                as[u] = *reinterpret_cast<const uint32_t*>(act + is); ao[u] = *reinterpret_cast<const uint32_t*>(act + io);
-                xs[u] = *reinterpret_cast<const float4*>(dX + is); xo[u] = *reinterpret_cast<const float4*>(dX + io);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = k0 + u * kz;
-            if (k < K) {
-                const float xsv[4] = {xs[u].x, xs[u].y, xs[u].z, xs[u].w}, xov[4] = {xo[u].x, xo[u].y, xo[u].z, xo[u].w};
-                float gs[4], go[4];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    gs[e] = ((as[u] >> (8 * e)) & 1u) ? xsv[e] * 0.5f / ds[sn[u]] : 0.f;
-                    go[e] = ((ao[u] >> (8 * e)) & 2u) ? xov[e] * 0.5f / dn_o[on[u]] : 0.f;
-                }
-                const int64_t ok = ((int64_t)b * K + k) * L + col;
-                subgc_store_act<4>(dF0, ok, gs, o16);
-                subgc_store_act<4>(dF1, ok, go, o16);
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------ relations <- nodes
-// grid (L/TC, B), TC = 128 columns; the image's F2/F3 node tiles [N x TC] are staged in LDS
-// (each node row is consumed by ~K/N relations per role), then every relation gathers from LDS.
-constexpr int TC = 128;
-template <bool VEC>
-__global__ __launch_bounds__(256) void gcn_edges_fwd_kernel(const float* __restrict__ F2, const float* __restrict__ F3,
-                                                            const int64_t* __restrict__ rel_ind,
-                                                            const float* __restrict__ skip, float* __restrict__ Pout,
-                                                            int B, int N, int K, int L) {
-    extern __shared__ __attribute__((aligned(16))) float sm_f[];
-    float* t2 = sm_f;                    // [N][TC]
-    float* t3 = sm_f + (size_t)N * TC;   // [N][TC]
-    int* ns = reinterpret_cast<int*>(t3 + (size_t)N * TC);   // [K]
-    int* no = ns + K;
-    const int b = blockIdx.y, c0 = blockIdx.x * TC;
-    const float cdiv1 = 1.f + 1e-7f;     // fp32(1 + 1e-7) = 1.00000012: rowsum of a 0/1 incidence row + 1e-7
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        int64_t s = rel_ind[((int64_t)b * K + k) * 2 + 0], o = rel_ind[((int64_t)b * K + k) * 2 + 1];
-        ns[k] = (int)(s < 0 ? 0 : (s >= N ? N - 1 : s));
-        no[k] = (int)(o < 0 ? 0 : (o >= N ? N - 1 : o));
-    }
-    const int items = N * (TC / 4);
-    for (int i0 = threadIdx.x; i0 < items; i0 += 4 * blockDim.x) {         // four node-row quads requested before the first is staged
-        float4 a[4], c[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = i0 + u * blockDim.x;
-            a[u] = make_float4(0.f, 0.f, 0.f, 0.f); c[u] = a[u];
-            if (i < items) {
-                const int n = i / (TC / 4), c4 = (i % (TC / 4)) * 4;
-                const int64_t g = ((int64_t)b * N + n) * L + c0 + c4;
-                if (c0 + c4 + 3 < L) {
-                    a[u] = *reinterpret_cast<const float4*>(F2 + g);
-                    c[u] = *reinterpret_cast<const float4*>(F3 + g);
-                } else {
-                    float* pa = &a[u].x; float* pc = &c[u].x;
-                    for (int j = 0; j < 4; ++j)
-                        if (c0 + c4 + j < L) { pa[j] = F2[g + j]; pc[j] = F3[g + j]; }
-                }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int i = i0 + u * blockDim.x;
-            if (i < items) {
-                const int n = i / (TC / 4), c4 = (i % (TC / 4)) * 4;
-                // relu(x / c) is what every consumer needs: do it once per node element
-                float4 x = a[u], y = c[u];
-                x.x = fmaxf(x.x / cdiv1, 0.f); x.y = fmaxf(x.y / cdiv1, 0.f); x.z = fmaxf(x.z / cdiv1, 0.f); x.w = fmaxf(x.w / cdiv1, 0.f);
-                y.x = fmaxf(y.x / cdiv1, 0.f); y.y = fmaxf(y.y / cdiv1, 0.f); y.z = fmaxf(y.z / cdiv1, 0.f); y.w = fmaxf(y.w / cdiv1, 0.f);
-                *reinterpret_cast<float4*>(t2 + n * TC + c4) = x;
-                *reinterpret_cast<float4*>(t3 + n * TC + c4) = y;
-            }
-        }
-    }
-    __syncthreads();
-    if (VEC) {                                                             // 8 relation streams x 32 lanes x 4 columns: 16-byte LDS reads and stores
-        const int cl4 = (threadIdx.x & 31) * 4, st = threadIdx.x >> 5;
-        if (c0 + cl4 >= L) return;
-        for (int k0 = st; k0 < K; k0 += 32) {
-            float4 v[4], sk[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + 8 * u;
-                if (k < K) {
-                    const float4 x = *reinterpret_cast<const float4*>(t2 + ns[k] * TC + cl4), y = *reinterpret_cast<const float4*>(t3 + no[k] * TC + cl4);
-                    v[u] = make_float4((x.x + y.x) / 2.f, (x.y + y.y) / 2.f, (x.z + y.z) / 2.f, (x.w + y.w) / 2.f);
-                    if (skip) sk[u] = *reinterpret_cast<const float4*>(skip + ((int64_t)b * K + k) * L + c0 + cl4);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + 8 * u;
-                if (k < K) {
-                    float4 r = v[u];
-                    if (skip) { r.x += sk[u].x; r.y += sk[u].y; r.z += sk[u].z; r.w += sk[u].w; }
-                    *reinterpret_cast<float4*>(Pout + ((int64_t)b * K + k) * L + c0 + cl4) = r;
-                }
-            }
-        }
-        return;
-    }
-    const int cl = threadIdx.x & (TC - 1), half = threadIdx.x >> 7;   // 2 relation streams x 128 columns
-    const int col = c0 + cl;
-    if (col >= L) return;
-    for (int k0 = half; k0 < K; k0 += 8) {                                 // four relations per round: LDS reads and skip loads in flight together
-        float v[4], sk[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = k0 + 2 * u;
-            if (k < K) {
-                v[u] = (t2[ns[k] * TC + cl] + t3[no[k] * TC + cl]) / 2.f;
-                sk[u] = skip ? skip[((int64_t)b * K + k) * L + col] : 0.f;
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = k0 + 2 * u;
-            if (k < K) Pout[((int64_t)b * K + k) * L + col] = skip ? v[u] + sk[u] : v[u];
-        }
-    }
-}
-
-// dF2[b,n,:] = 1/2 [F2>0] / c * sum_{k in CSR_s(n)} dP[b,k,:]   (and F3 / CSR_o)
-__global__ __launch_bounds__(256) void gcn_edges_bwd_kernel(const float* __restrict__ dP, const float* __restrict__ F2,
-                                                            const float* __restrict__ F3, const int32_t* __restrict__ ptr,
-                                                            const int32_t* __restrict__ edges, float* __restrict__ dF2,
-                                                            float* __restrict__ dF3, int B, int N, int K, int L) {
-    extern __shared__ int sm_i[];
-    int* ps = sm_i; int* po = ps + (N + 1); int* es = po + (N + 1); int* eo = es + K;
-    const int b = blockIdx.y;
-    for (int i = threadIdx.x; i <= N; i += blockDim.x) {
-        ps[i] = ptr[((int64_t)0 * B + b) * (N + 1) + i];
-        po[i] = ptr[((int64_t)1 * B + b) * (N + 1) + i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-        es[i] = edges[((int64_t)0 * B + b) * K + i];
-        eo[i] = edges[((int64_t)1 * B + b) * K + i];
-    }
-    __syncthreads();
-    const int col = blockIdx.x * 256 + threadIdx.x;
-    if (col >= L) return;
-    const float cdiv1 = 1.f + 1e-7f;
-    const float* dp = dP + (int64_t)b * K * L + col;
-    for (int n = blockIdx.z; n < N; n += gridDim.z) {
-        float a = 0.f, c = 0.f;
-        for (int j = ps[n]; j < ps[n + 1]; ++j) a += dp[(int64_t)es[j] * L];
-        for (int j = po[n]; j < po[n + 1]; ++j) c += dp[(int64_t)eo[j] * L];
-        const int64_t o = ((int64_t)b * N + n) * L + col;
-        dF2[o] = (F2[o] / cdiv1 > 0.f) ? a * 0.5f / cdiv1 : 0.f;
-        dF3[o] = (F3[o] / cdiv1 > 0.f) ? c * 0.5f / cdiv1 : 0.f;
-    }
-}
-
-__global__ __launch_bounds__(256) void gcn_edges_bwd_vec_kernel(const float* __restrict__ dP, const float* __restrict__ F2,
-                                                                const float* __restrict__ F3, const int32_t* __restrict__ ptr,
-                                                                const int32_t* __restrict__ edges, float* __restrict__ dF2,
-                                                                float* __restrict__ dF3, int B, int N, int K, int L) {
-    extern __shared__ int sm_i[];
-    int* ps = sm_i; int* po = ps + (N + 1); int* es = po + (N + 1); int* eo = es + K;
-    const int b = blockIdx.y;
-    for (int i = threadIdx.x; i <= N; i += blockDim.x) {
-        ps[i] = ptr[((int64_t)0 * B + b) * (N + 1) + i];
-        po[i] = ptr[((int64_t)1 * B + b) * (N + 1) + i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-        es[i] = edges[((int64_t)0 * B + b) * K + i];
-        eo[i] = edges[((int64_t)1 * B + b) * K + i];
-    }
-    __syncthreads();
-    const int col = (blockIdx.x * 256 + threadIdx.x) * 4;
-    if (col >= L) return;
-    const float cdiv1 = 1.f + 1e-7f;
-    const float* dp = dP + (int64_t)b * K * L + col;
-    for (int n = blockIdx.z; n < N; n += gridDim.z) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), c = a;
-        const int64_t o = ((int64_t)b * N + n) * L + col;
-        const float4 f2 = *reinterpret_cast<const float4*>(F2 + o), f3 = *reinterpret_cast<const float4*>(F3 + o);
-        auto row = [&](int e) { return *reinterpret_cast<const float4*>(dp + (int64_t)e * L); };
-        gather_pair(es, ps[n], ps[n + 1], row, eo, po[n], po[n + 1], row, a, c);
-        float4 r2, r3;
-        r2.x = (f2.x / cdiv1 > 0.f) ? a.x * 0.5f / cdiv1 : 0.f; r2.y = (f2.y / cdiv1 > 0.f) ? a.y * 0.5f / cdiv1 : 0.f;
-        r2.z = (f2.z / cdiv1 > 0.f) ? a.z * 0.5f / cdiv1 : 0.f; r2.w = (f2.w / cdiv1 > 0.f) ? a.w * 0.5f / cdiv1 : 0.f;
-        r3.x = (f3.x / cdiv1 > 0.f) ? c.x * 0.5f / cdiv1 : 0.f; r3.y = (f3.y / cdiv1 > 0.f) ? c.y * 0.5f / cdiv1 : 0.f;
-        r3.z = (f3.z / cdiv1 > 0.f) ? c.z * 0.5f / cdiv1 : 0.f; r3.w = (f3.w / cdiv1 > 0.f) ? c.w * 0.5f / cdiv1 : 0.f;
-        *reinterpret_cast<float4*>(dF2 + o) = r2;
-        *reinterpret_cast<float4*>(dF3 + o) = r3;
     }
 }
 
@@ -696,10 +344,6 @@ __global__ void zero_f32_kernel(float* p, int64_t n) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = 0.f;
 }
 
-inline bool gcn_vec_ok(int L, const void* a, const void* b, const void* c, const void* d) {
-    auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-    return L % 4 == 0 && al(a) && al(b) && al(c) && al(d);
-}
 inline bool bn_vec_ok(int C, const void* a, const void* b, const void* c) {
     auto al = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     return C % 4 == 0 && al(a) && al(b) && al(c);
@@ -710,8 +354,6 @@ inline int bn_rows_per_block(int M, int C) {
     const int slabs = std::max(1, 512 / col_groups);
     return std::max(16, (M + slabs - 1) / slabs);
 }
-
-inline int raise_lds(const void* fn, size_t bytes, const char* what) { return subgc::raise_lds_cached(fn, bytes, what); }
 
 }  // namespace
 
@@ -740,73 +382,6 @@ SUBGC_API int subgc_csr_build(const int64_t* rel_ind, int B, int K, int N, int32
     const size_t lds = sizeof(int) * (K + N + 1);
     hipLaunchKernelGGL(csr_build_kernel, dim3(B, 2), dim3(128), lds, (hipStream_t)stream, rel_ind, B, K, N, ptr, edges);
     return subgc::check_launch("subgc_csr_build");
-}
-
-SUBGC_API int subgc_gcn_nodes_fwd(const float* F0, const float* F1, const int32_t* ptr, const int32_t* edges, const float* skip,
-                                  float* Xout, uint8_t* act, int B, int N, int K, int L, void* stream) {
-    SUBGC_REQUIRE(B >= 0 && N > 0 && K > 0 && L > 0, "gcn_nodes_fwd: bad sizes");
-    if (B == 0) return SUBGC_OK;
-    SUBGC_REQUIRE(F0 && F1 && ptr && edges && Xout, "gcn_nodes_fwd: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    subgc::ProfScope prof(SUBGC_FAM_GCN, s, 4.0 * B * L * (2.0 * K + (skip ? 2.0 : 1.0) * N));
-    const size_t lds = sizeof(int) * (2 * (N + 1) + 2 * K);
-    if (gcn_vec_ok(L, F0, F1, skip, Xout) && (reinterpret_cast<uintptr_t>(act) & 3) == 0)
-        hipLaunchKernelGGL(gcn_nodes_fwd_vec_kernel, dim3((L / 4 + 255) / 256, B, subgc::gcn_zsplit((L / 4 + 255) / 256, B, N)), dim3(256), lds, s, F0, F1, ptr, edges, skip, Xout, act, B, N, K, L);
-    else
-        hipLaunchKernelGGL(gcn_nodes_fwd_kernel, dim3((L + 255) / 256, B, subgc::gcn_zsplit((L + 255) / 256, B, N)), dim3(256), lds, s, F0, F1, ptr, edges, skip, Xout, act, B, N, K, L);
-    return subgc::check_launch("subgc_gcn_nodes_fwd");
-}
-
-SUBGC_API int subgc_gcn_nodes_bwd(const float* dX, const uint8_t* act, const int64_t* rel_ind, const int32_t* ptr, void* dF0,
-                                  void* dF1, int out_bf16, int B, int N, int K, int L, void* stream) {
-    SUBGC_REQUIRE(B >= 0 && N > 0 && K > 0 && L > 0, "gcn_nodes_bwd: bad sizes");
-    if (B == 0) return SUBGC_OK;
-    SUBGC_REQUIRE(dX && act && rel_ind && ptr && dF0 && dF1, "gcn_nodes_bwd: null pointer");
-    SUBGC_DEBUG_RANGE(rel_ind, 8, (int64_t)B * K, 2, 2, 0, N - 1, -1, "gcn_nodes_bwd: rel_ind", stream);
-    hipStream_t s = (hipStream_t)stream;
-    subgc::ProfScope prof(SUBGC_FAM_GCN, s, 4.0 * B * L * (2.0 * K + 2.0 * K));
-    const size_t lds = sizeof(int) * (2 * K) + sizeof(float) * 2 * N;
-    const bool vec = gcn_vec_ok(L, dX, nullptr, nullptr, nullptr) && (reinterpret_cast<uintptr_t>(act) & 3) == 0 &&
-                     ((reinterpret_cast<uintptr_t>(dF0) | reinterpret_cast<uintptr_t>(dF1)) & (out_bf16 ? 7 : 15)) == 0;
-    SUBGC_REQUIRE(vec || !out_bf16, "gcn_nodes_bwd: bf16 gradients need L %% 4 == 0 and aligned rows");
-    if (vec)
-        hipLaunchKernelGGL(gcn_nodes_bwd_vec_kernel, dim3((L / 4 + 255) / 256, B, subgc::gcn_zsplit((L / 4 + 255) / 256, B, (K + 3) / 4)), dim3(256), lds, s, dX, act, rel_ind, ptr, dF0, dF1, B, N, K, L, out_bf16);
-    else
-        hipLaunchKernelGGL(gcn_nodes_bwd_kernel, dim3((L + 255) / 256, B, subgc::gcn_zsplit((L + 255) / 256, B, K)), dim3(256), lds, s, dX, act, rel_ind, ptr, static_cast<float*>(dF0), static_cast<float*>(dF1), B, N, K, L);
-    return subgc::check_launch("subgc_gcn_nodes_bwd");
-}
-
-SUBGC_API int subgc_gcn_edges_fwd(const float* F2, const float* F3, const int64_t* rel_ind, const float* skip, float* Pout, int B,
-                                  int N, int K, int L, void* stream) {
-    SUBGC_REQUIRE(B >= 0 && N > 0 && K > 0 && L > 0, "gcn_edges_fwd: bad sizes");
-    if (B == 0) return SUBGC_OK;
-    SUBGC_REQUIRE(F2 && F3 && rel_ind && Pout, "gcn_edges_fwd: null pointer");
-    SUBGC_DEBUG_RANGE(rel_ind, 8, (int64_t)B * K, 2, 2, 0, N - 1, -1, "gcn_edges_fwd: rel_ind", stream);
-    SUBGC_REQUIRE(L % 4 == 0, "gcn_edges_fwd: L must be a multiple of 4 (got %d)", L);
-    hipStream_t s = (hipStream_t)stream;
-    const size_t lds = sizeof(float) * 2 * (size_t)N * TC + sizeof(int) * 2 * K;
-    const bool vec = gcn_vec_ok(L, Pout, skip, nullptr, nullptr);
-    int rc = vec ? raise_lds((const void*)gcn_edges_fwd_kernel<true>, lds, "gcn_edges_fwd") : raise_lds((const void*)gcn_edges_fwd_kernel<false>, lds, "gcn_edges_fwd");
-    if (rc) return rc;
-    subgc::ProfScope prof(SUBGC_FAM_GCN, s, 4.0 * B * L * (2.0 * N + (skip ? 2.0 : 1.0) * K));
-    if (vec) hipLaunchKernelGGL(gcn_edges_fwd_kernel<true>, dim3((L + TC - 1) / TC, B), dim3(256), lds, s, F2, F3, rel_ind, skip, Pout, B, N, K, L);
-    else hipLaunchKernelGGL(gcn_edges_fwd_kernel<false>, dim3((L + TC - 1) / TC, B), dim3(256), lds, s, F2, F3, rel_ind, skip, Pout, B, N, K, L);
-    return subgc::check_launch("subgc_gcn_edges_fwd");
-}
-
-SUBGC_API int subgc_gcn_edges_bwd(const float* dP, const float* F2, const float* F3, const int32_t* ptr, const int32_t* edges,
-                                  float* dF2, float* dF3, int B, int N, int K, int L, void* stream) {
-    SUBGC_REQUIRE(B >= 0 && N > 0 && K > 0 && L > 0, "gcn_edges_bwd: bad sizes");
-    if (B == 0) return SUBGC_OK;
-    SUBGC_REQUIRE(dP && F2 && F3 && ptr && edges && dF2 && dF3, "gcn_edges_bwd: null pointer");
-    hipStream_t s = (hipStream_t)stream;
-    subgc::ProfScope prof(SUBGC_FAM_GCN, s, 4.0 * B * L * (2.0 * K + 4.0 * N));
-    const size_t lds = sizeof(int) * (2 * (N + 1) + 2 * K);
-    if (gcn_vec_ok(L, dP, F2, F3, dF2) && (reinterpret_cast<uintptr_t>(dF3) & 15) == 0)
-        hipLaunchKernelGGL(gcn_edges_bwd_vec_kernel, dim3((L / 4 + 255) / 256, B, subgc::gcn_zsplit((L / 4 + 255) / 256, B, N)), dim3(256), lds, s, dP, F2, F3, ptr, edges, dF2, dF3, B, N, K, L);
-    else
-        hipLaunchKernelGGL(gcn_edges_bwd_kernel, dim3((L + 255) / 256, B, subgc::gcn_zsplit((L + 255) / 256, B, N)), dim3(256), lds, s, dP, F2, F3, ptr, edges, dF2, dF3, B, N, K, L);
-    return subgc::check_launch("subgc_gcn_edges_bwd");
 }
 
 SUBGC_API int subgc_bn_fwd(const float* X, float* Y, int M, int C, const float* gamma, const float* beta, float* running_mean,
@@ -893,7 +468,7 @@ SUBGC_API int subgc_bn_bwd(const float* dY, const float* X, const float* gamma, 
 
 // ------------------------------------------------------------------ aggregate first (include/subgc_gcn_agg_hip.h)
 // Collection units without BatchNorm are linear in front of their ReLU, so the 0/1 map is applied to the SOURCE rows and the two Linear
-// layers run on the (fewer) target rows.  gcn_agg_fwd_kernel is the gather of gcn_nodes_fwd_vec_kernel (CSR lists in LDS, float4 rows, four
+// layers run on the (fewer) target rows.  gcn_agg_fwd_kernel is the gather of gcn_nodes_fwd_f4_kernel (CSR lists in LDS, float4 rows, four
 // rows of each role requested at a time) without its ReLU / role-average / residual epilogue: both roles read the SAME source X.
 #include "../../include/subgc_gcn_agg_hip.h"
 
@@ -903,16 +478,9 @@ __global__ __launch_bounds__(256) void gcn_agg_fwd_kernel(const float* __restric
                                                           const int32_t* __restrict__ edges, float* __restrict__ A0, float* __restrict__ A1,
                                                           float* __restrict__ s0, float* __restrict__ s1, int B, int N, int K, int L) {
     extern __shared__ int sm_i[];
-    int* ps = sm_i; int* po = ps + (N + 1); int* es = po + (N + 1); int* eo = es + K;
+    int *ps, *po, *es, *eo;
     const int b = blockIdx.y;
-    for (int i = threadIdx.x; i <= N; i += blockDim.x) {
-        ps[i] = ptr[((int64_t)0 * B + b) * (N + 1) + i];
-        po[i] = ptr[((int64_t)1 * B + b) * (N + 1) + i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-        es[i] = edges[((int64_t)0 * B + b) * K + i];
-        eo[i] = edges[((int64_t)1 * B + b) * K + i];
-    }
+    gcn_stage_csr(sm_i, ptr, edges, b, B, N, K, ps, po, es, eo);
     __syncthreads();
     const int col = (blockIdx.x * 256 + threadIdx.x) * 4;
     const float* x = X + (int64_t)b * K * L + col;
@@ -941,16 +509,10 @@ __global__ __launch_bounds__(256) void gcn_agg_bwd_kernel(const float* __restric
     int* ns = sm_i; int* no = ns + K;
     float* w0 = reinterpret_cast<float*>(no + K); float* w1 = w0 + N;
     const int b = blockIdx.y;
-    for (int k = threadIdx.x; k < K; k += blockDim.x) {
-        int64_t s = rel_ind[((int64_t)b * K + k) * 2 + 0], o = rel_ind[((int64_t)b * K + k) * 2 + 1];
-        ns[k] = (int)(s < 0 ? 0 : (s >= N ? N - 1 : s));
-        no[k] = (int)(o < 0 ? 0 : (o >= N ? N - 1 : o));
-    }
-    for (int n = threadIdx.x; n < N; n += blockDim.x) {
-        const int32_t* p0 = ptr + ((int64_t)0 * B + b) * (N + 1);
-        const int32_t* p1 = ptr + ((int64_t)1 * B + b) * (N + 1);
-        w0[n] = 0.5f / ((float)(p0[n + 1] - p0[n]) + 1e-7f);
-        w1[n] = 0.5f / ((float)(p1[n + 1] - p1[n]) + 1e-7f);
+    gcn_stage_rel_nodes(rel_ind, ptr, b, B, N, K, ns, no, w0, w1);         // w = cnt + 1e-7, each thread its own nodes ...
+    for (int n = threadIdx.x; n < N; n += blockDim.x) {                    // ... which it turns into the weights 0.5 / (cnt + 1e-7)
+        w0[n] = 0.5f / w0[n];
+        w1[n] = 0.5f / w1[n];
     }
     __syncthreads();
     const int col = (blockIdx.x * 256 + threadIdx.x) * 4;

@@ -368,28 +368,6 @@ class ClassTableFn(Function):
 
 
 # ------------------------------------------------------------------------------- GCN
-class GcnNodesFn(Function):
-    """nodes <- relations (graph_conv_unit.py:34-36 for units 0,1 + graph_conv.py:26 + residual)."""
-
-    @staticmethod
-    def forward(ctx, F0, F1, skip, rel_ind, ptr, edges, N):
-        B, K, L = F0.shape
-        F0, F1 = F0.contiguous(), F1.contiguous()
-        out, act = ops.gcn_nodes_fwd(F0, F1, ptr, edges, skip.contiguous() if skip is not None else None, B, N, K, L)
-        ctx.save_for_backward(act, rel_ind, ptr)
-        ctx.dims = (B, N, K, L)
-        ctx.has_skip = skip is not None
-        return out
-
-    @staticmethod
-    def backward(ctx, dX):
-        act, rel_ind, ptr = ctx.saved_tensors
-        B, N, K, L = ctx.dims
-        dX = dX.contiguous()
-        dF0, dF1 = ops.gcn_nodes_bwd(dX, act, rel_ind, ptr, B, N, K, L)
-        return dF0, dF1, (dX if ctx.has_skip else None), None, None, None, None
-
-
 class GcnAggFirstFn(Function):
     """nodes <- relations for a layer WITHOUT BatchNorm, aggregation first (ops.GCN_AGGREGATE_FIRST; units 0,1 of graph_conv.py:24-26 and
     the residual, graph_conv_unit.py:28-36 with gcn_bn = 0).  Everything in front of a unit's ReLU is linear, and the targets (B * N node
@@ -470,83 +448,6 @@ def gcn_aggregate_first_ok(gcn_bn, bf16, B, N, K, L):
     return bool(ops.GCN_AGGREGATE_FIRST) and not gcn_bn and not bf16 and N < K and L % 4 == 0
 
 
-class GcnNodesB16Fn(Function):
-    """GcnNodesFn for bf16-STORED unit outputs (compute_dtype = bf16, no BatchNorm: Sub-GC presets): the normalise-on-load kernels with the
-    identity triple read the bf16 GEMM results as they are, d(y) leaves the backward in bf16 (what the Linear backward's GEMMs consume),
-    and the result's bf16 copy for the next layer's GEMM comes out of the same launch (`want16`) -- no fp32 unit outputs, no cast passes."""
-
-    @staticmethod
-    def forward(ctx, y0, y1, skip, rel_ind, ptr, edges, N, want16):
-        B, K, L = y0.shape
-        y0, y1 = y0.contiguous(), y1.contiguous()
-        ident = ops.identity_aff(L, y0.device)
-        out, out16, act = ops.gcn_nodes_fwd_bn(y0, y1, ident, ident, ptr, edges, skip.contiguous() if skip is not None else None, B, N, K, L, want16)
-        ctx.save_for_backward(act, rel_ind, ptr)
-        ctx.dims, ctx.has_skip = (B, N, K, L), skip is not None
-        if want16:
-            ctx.mark_non_differentiable(out16)
-            ctx.set_materialize_grads(False)
-            return out, out16
-        return out
-
-    @staticmethod
-    def backward(ctx, dX, *_unused):
-        act, rel_ind, ptr = ctx.saved_tensors
-        B, N, K, L = ctx.dims
-        dX = dX.contiguous()
-        dy0, dy1 = ops.gcn_nodes_bwd(dX, act, rel_ind, ptr, B, N, K, L, bf16=True)
-        return dy0, dy1, (dX if ctx.has_skip else None), None, None, None, None, None
-
-
-class GcnEdgesB16Fn(Function):
-    """GcnEdgesFn for bf16-stored unit outputs (see GcnNodesB16Fn)."""
-
-    @staticmethod
-    def forward(ctx, y2, y3, skip, rel_ind, ptr, edges, K, want16):
-        B, N, L = y2.shape
-        y2, y3 = y2.contiguous(), y3.contiguous()
-        ident = ops.identity_aff(L, y2.device)
-        out, out16 = ops.gcn_edges_fwd_bn(y2, y3, ident, ident, rel_ind, skip.contiguous() if skip is not None else None, B, N, K, L, want16)
-        ctx.save_for_backward(y2, y3, ptr, edges)
-        ctx.dims, ctx.has_skip = (B, N, K, L), skip is not None
-        if want16:
-            ctx.mark_non_differentiable(out16)
-            ctx.set_materialize_grads(False)
-            return out, out16
-        return out
-
-    @staticmethod
-    def backward(ctx, dP, *_unused):
-        y2, y3, ptr, edges = ctx.saved_tensors
-        B, N, K, L = ctx.dims
-        dP = dP.contiguous()
-        ident = ops.identity_aff(L, dP.device)
-        dy2, dy3 = ops.gcn_edges_bwd_bn(dP, y2, y3, ident, ident, ptr, edges, B, N, K, L, bf16=True)
-        return dy2, dy3, (dP if ctx.has_skip else None), None, None, None, None, None
-
-
-class GcnEdgesFn(Function):
-    """relations <- nodes (units 2,3; LDS-staged gather)."""
-
-    @staticmethod
-    def forward(ctx, F2, F3, skip, rel_ind, ptr, edges, K):
-        B, N, L = F2.shape
-        F2, F3 = F2.contiguous(), F3.contiguous()
-        out = ops.gcn_edges_fwd(F2, F3, rel_ind, skip.contiguous() if skip is not None else None, B, N, K, L)
-        ctx.save_for_backward(F2, F3, ptr, edges)
-        ctx.dims = (B, N, K, L)
-        ctx.has_skip = skip is not None
-        return out
-
-    @staticmethod
-    def backward(ctx, dP):
-        F2, F3, ptr, edges = ctx.saved_tensors
-        B, N, K, L = ctx.dims
-        dP = dP.contiguous()
-        dF2, dF3 = ops.gcn_edges_bwd(dP, F2, F3, ptr, edges, B, N, K, L)
-        return dF2, dF3, (dP if ctx.has_skip else None), None, None, None, None
-
-
 def _bn_back(dFh, y, gamma, beta, aff, rstd):
     """BatchNorm backward of one fused source: d(normalised) -> d(raw unit output) in its storage type; the affine gradients go
     straight into the flat bucket when it exists (returns (dy, dgamma, dbeta) with None for what was written in place)."""
@@ -570,68 +471,100 @@ def _bn_back_pair(dFa, dFb, ya, yb, ga, ba, gb_, bb, affa, affb, rstda, rstdb):
     return _bn_back(dFa, ya, ga, ba, affa, rstda), _bn_back(dFb, yb, gb_, bb, affb, rstdb)
 
 
-class GcnNodesBnFn(Function):
-    """nodes <- relations (GcnNodesFn) with the BatchNorm1d of the two collection units (graph_conv_unit.py:31-32) fused in: y0, y1
-    are the RAW unit outputs (fp32, or bf16 under compute_dtype = bf16); the batch statistics are one pass, the aggregation kernel
-    normalises on load, the backward returns d(y) in y's storage type.  `want16`: also a bf16 copy of the result (non-differentiable)."""
+def _with16(ctx, out, out16, want16):
+    """What a Gcn*Fn forward returns: `out`, or (out, its bf16 copy) under `want16` -- the copy is not differentiable."""
+    if not want16:
+        return out
+    ctx.mark_non_differentiable(out16)
+    ctx.set_materialize_grads(False)          # else autograd hands the backward a zero tensor for the bf16 copy (an ATen fill per call)
+    return out, out16
+
+
+class GcnNodesFn(Function):
+    """nodes <- relations (graph_conv_unit.py:34-36 for units 0,1 + graph_conv.py:26 + residual).  y0, y1 [B, K, L] are the two unit
+    outputs, fp32 or bf16-STORED (compute_dtype = bf16: the kernels read the bf16 GEMM results as they are and d(y) leaves the backward in
+    bf16, what the Linear backward's GEMMs consume -- no fp32 unit outputs, no cast passes).
+    g0, b0, g1, b1, stats, training given (`AttModel._bn_args`; all None without BatchNorm): the BatchNorm1d of the two units
+    (graph_conv_unit.py:31-32) is fused in -- y0, y1 are the RAW unit outputs, the batch statistics are one pass, the aggregation kernel
+    normalises on load, the backward returns d(y) in y's storage type.
+    `want16`: also a bf16 copy of the result for the next layer's GEMM, out of the same launch -> (out, out16)."""
 
     @staticmethod
-    def forward(ctx, y0, y1, skip, rel_ind, ptr, edges, N, g0, b0, g1, b1, stats, training, want16):
+    def forward(ctx, y0, y1, skip, rel_ind, ptr, edges, N, g0=None, b0=None, g1=None, b1=None, stats=None, training=None, want16=False):
         B, K, L = y0.shape
         y0, y1 = y0.contiguous(), y1.contiguous()
-        (aff0, rstd0), (aff1, rstd1) = ops.bn_stats_pair(y0.view(B * K, L), y1.view(B * K, L), g0, b0, stats[0], stats[1], g1, b1, stats[2], stats[3], training)
-        out, out16, act = ops.gcn_nodes_fwd_bn(y0, y1, aff0, aff1, ptr, edges, skip.contiguous() if skip is not None else None, B, N, K, L, want16)
-        ctx.save_for_backward(y0, y1, aff0, rstd0, aff1, rstd1, act, rel_ind, ptr)
+        skip_c = skip.contiguous() if skip is not None else None
+        bn, y16 = g0 is not None, ops.is_b16(y0)
+        aff0 = aff1 = out16 = None
+        if bn:
+            (aff0, rstd0), (aff1, rstd1) = ops.bn_stats_pair(y0.view(B * K, L), y1.view(B * K, L), g0, b0, stats[0], stats[1], g1, b1, stats[2], stats[3], training)
+        if bn or y16 or want16:
+            out, out16, act = ops.gcn_nodes_fwd_bn(y0, y1, aff0, aff1, ptr, edges, skip_c, B, N, K, L, want16)
+        else:
+            out, act = ops.gcn_nodes_fwd(y0, y1, ptr, edges, skip_c, B, N, K, L)       # any L and alignment (scalar fallback)
+        ctx.save_for_backward(act, rel_ind, ptr, *((y0, y1, aff0, rstd0, aff1, rstd1) if bn else ()))
         ctx.params = (g0, b0, g1, b1)
-        ctx.dims, ctx.has_skip, ctx.training = (B, N, K, L), skip is not None, training
-        if want16:
-            ctx.mark_non_differentiable(out16)
-            ctx.set_materialize_grads(False)          # else autograd hands the backward a zero tensor for the bf16 copy (an ATen fill per call)
-            return out, out16
-        return out
+        ctx.dims, ctx.has_skip, ctx.training, ctx.y16 = (B, N, K, L), skip is not None, training, y16
+        return _with16(ctx, out, out16, want16)
 
     @staticmethod
     def backward(ctx, dX, *_unused):
-        y0, y1, aff0, rstd0, aff1, rstd1, act, rel_ind, ptr = ctx.saved_tensors
-        if not ctx.training:
-            raise RuntimeError("GcnNodesBnFn: backward in eval mode is not part of the Sub-GC path")
+        act, rel_ind, ptr, *bn = ctx.saved_tensors
+        if bn and not ctx.training:
+            raise RuntimeError("GcnNodesFn: backward in eval mode is not part of the Sub-GC path")
         B, N, K, L = ctx.dims
-        g0, b0, g1, b1 = ctx.params
         dX = dX.contiguous()
+        dskip = dX if ctx.has_skip else None
+        if not bn:
+            dy0, dy1 = ops.gcn_nodes_bwd(dX, act, rel_ind, ptr, B, N, K, L, bf16=ctx.y16)
+            return (dy0, dy1, dskip) + (None,) * 11
+        y0, y1, aff0, rstd0, aff1, rstd1 = bn
+        g0, b0, g1, b1 = ctx.params
         dF0, dF1 = ops.gcn_nodes_bwd(dX, act, rel_ind, ptr, B, N, K, L)
         (dy0, dg0, db0), (dy1, dg1, db1) = _bn_back_pair(dF0, dF1, y0, y1, g0, b0, g1, b1, aff0, aff1, rstd0, rstd1)
-        return dy0, dy1, (dX if ctx.has_skip else None), None, None, None, None, dg0, db0, dg1, db1, None, None, None
+        return dy0, dy1, dskip, None, None, None, None, dg0, db0, dg1, db1, None, None, None
 
 
-class GcnEdgesBnFn(Function):
-    """relations <- nodes (GcnEdgesFn) with the two units' BatchNorm fused in (see GcnNodesBnFn)."""
+class GcnEdgesFn(Function):
+    """relations <- nodes (units 2,3; LDS-staged gather): y2, y3 [B, N, L] -> [B, K, L]; arguments as GcnNodesFn."""
 
     @staticmethod
-    def forward(ctx, y2, y3, skip, rel_ind, ptr, edges, K, g2, b2, g3, b3, stats, training, want16):
+    def forward(ctx, y2, y3, skip, rel_ind, ptr, edges, K, g2=None, b2=None, g3=None, b3=None, stats=None, training=None, want16=False):
         B, N, L = y2.shape
         y2, y3 = y2.contiguous(), y3.contiguous()
-        (aff2, rstd2), (aff3, rstd3) = ops.bn_stats_pair(y2.view(B * N, L), y3.view(B * N, L), g2, b2, stats[0], stats[1], g3, b3, stats[2], stats[3], training)
-        out, out16 = ops.gcn_edges_fwd_bn(y2, y3, aff2, aff3, rel_ind, skip.contiguous() if skip is not None else None, B, N, K, L, want16)
-        ctx.save_for_backward(y2, y3, aff2, rstd2, aff3, rstd3, ptr, edges)
+        skip_c = skip.contiguous() if skip is not None else None
+        bn = g2 is not None
+        aff2 = aff3 = out16 = None
+        if bn:
+            (aff2, rstd2), (aff3, rstd3) = ops.bn_stats_pair(y2.view(B * N, L), y3.view(B * N, L), g2, b2, stats[0], stats[1], g3, b3, stats[2], stats[3], training)
+        if bn or ops.is_b16(y2) or want16:
+            out, out16 = ops.gcn_edges_fwd_bn(y2, y3, aff2, aff3, rel_ind, skip_c, B, N, K, L, want16)
+        else:
+            out = ops.gcn_edges_fwd(y2, y3, rel_ind, skip_c, B, N, K, L)
+        ctx.save_for_backward(y2, y3, ptr, edges, *((aff2, rstd2, aff3, rstd3) if bn else ()))
         ctx.params = (g2, b2, g3, b3)
         ctx.dims, ctx.has_skip, ctx.training = (B, N, K, L), skip is not None, training
-        if want16:
-            ctx.mark_non_differentiable(out16)
-            ctx.set_materialize_grads(False)          # else autograd hands the backward a zero tensor for the bf16 copy (an ATen fill per call)
-            return out, out16
-        return out
+        return _with16(ctx, out, out16, want16)
 
     @staticmethod
     def backward(ctx, dP, *_unused):
-        y2, y3, aff2, rstd2, aff3, rstd3, ptr, edges = ctx.saved_tensors
-        if not ctx.training:
-            raise RuntimeError("GcnEdgesBnFn: backward in eval mode is not part of the Sub-GC path")
+        y2, y3, ptr, edges, *bn = ctx.saved_tensors
+        if bn and not ctx.training:
+            raise RuntimeError("GcnEdgesFn: backward in eval mode is not part of the Sub-GC path")
         B, N, K, L = ctx.dims
-        g2, b2, g3, b3 = ctx.params
         dP = dP.contiguous()
+        dskip = dP if ctx.has_skip else None
+        if not bn:
+            if ops.is_b16(y2):
+                dy2, dy3 = ops.gcn_edges_bwd_bn(dP, y2, y3, None, None, ptr, edges, B, N, K, L, bf16=True)
+            else:
+                dy2, dy3 = ops.gcn_edges_bwd(dP, y2, y3, ptr, edges, B, N, K, L)
+            return (dy2, dy3, dskip) + (None,) * 11
+        aff2, rstd2, aff3, rstd3 = bn
+        g2, b2, g3, b3 = ctx.params
         dF2, dF3 = ops.gcn_edges_bwd_bn(dP, y2, y3, aff2, aff3, ptr, edges, B, N, K, L)
         (dy2, dg2, db2), (dy3, dg3, db3) = _bn_back_pair(dF2, dF3, y2, y3, g2, b2, g3, b3, aff2, aff3, rstd2, rstd3)
-        return dy2, dy3, (dP if ctx.has_skip else None), None, None, None, None, dg2, db2, dg3, db3, None, None, None
+        return dy2, dy3, dskip, None, None, None, None, dg2, db2, dg3, db3, None, None, None
 
 
 class BatchNormFn(Function):

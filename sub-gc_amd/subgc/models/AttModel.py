@@ -559,8 +559,10 @@ class AttModel(CaptionModel):
             x16n = p16n = None
             fuse = self.GCN_use_bn and L % 4 == 0
             raw16 = w16 is not None and not self.GCN_use_bn and L % 8 == 0                  # bf16 storage, no BatchNorm: unit outputs stay bf16
-            nxt_x = w16 is not None and l + 1 < self.GCN_layers and live_edges[l + 1]          # the next layer reads new_x as a GEMM operand
-            nxt_p = w16 is not None and l + 1 < self.GCN_layers and live_nodes[l + 1]
+            no_bn = (None,) * 6                                                                # in place of `_bn_args`
+            # the next layer reads new_x / new_p as a GEMM operand: its bf16 copy comes out of the aggregation launch
+            nxt_x = (fuse or raw16) and w16 is not None and l + 1 < self.GCN_layers and live_edges[l + 1]
+            nxt_p = (fuse or raw16) and w16 is not None and l + 1 < self.GCN_layers and live_nodes[l + 1]
             if live_nodes[l] and F_.gcn_aggregate_first_ok(self.GCN_use_bn, w16 is not None, B, N, K, L):
                 # no BatchNorm and fewer node rows than relation rows: aggregate the source rows, then fc_lft / fc_rgt on B * N rows per
                 # role (functions.GcnAggFirstFn) -- the paired and the unit-by-unit configuration share this order
@@ -569,24 +571,12 @@ class AttModel(CaptionModel):
                 new_x = F_.GcnAggFirstFn.apply(ps[0].reshape(B * K, L), skip_x if res else None, rel_ind, ptr, edges, B, N, K, *pu)
             elif live_nodes[l]:
                 y0, y1 = self._unit_pair(l, 0, ps[0], p16, flat16, fuse, raw16)
-                if fuse:
-                    r = F_.GcnNodesBnFn.apply(y0, y1, skip_x if res else None, rel_ind, ptr, edges, N, *self._bn_args(l, 0, 1), nxt_x)
-                    new_x, x16n = (r[0], r[1].view(B * N, L)) if nxt_x else (r, None)
-                elif raw16:
-                    r = F_.GcnNodesB16Fn.apply(y0, y1, skip_x if res else None, rel_ind, ptr, edges, N, nxt_x)
-                    new_x, x16n = (r[0], r[1].view(B * N, L)) if nxt_x else (r, None)
-                else:
-                    new_x = F_.GcnNodesFn.apply(y0, y1, skip_x if res else None, rel_ind, ptr, edges, N)
+                r = F_.GcnNodesFn.apply(y0, y1, skip_x if res else None, rel_ind, ptr, edges, N, *(self._bn_args(l, 0, 1) if fuse else no_bn), nxt_x)
+                new_x, x16n = (r[0], r[1].view(B * N, L)) if nxt_x else (r, None)
             if live_edges[l]:
                 y2, y3 = self._unit_pair(l, 2, xs[0], x16, flat16, fuse, raw16)
-                if fuse:
-                    r = F_.GcnEdgesBnFn.apply(y2, y3, skip_p if res else None, rel_ind, ptr, edges, K, *self._bn_args(l, 2, 3), nxt_p)
-                    new_p, p16n = (r[0], r[1].view(B * K, L)) if nxt_p else (r, None)
-                elif raw16:
-                    r = F_.GcnEdgesB16Fn.apply(y2, y3, skip_p if res else None, rel_ind, ptr, edges, K, nxt_p)
-                    new_p, p16n = (r[0], r[1].view(B * K, L)) if nxt_p else (r, None)
-                else:
-                    new_p = F_.GcnEdgesFn.apply(y2, y3, skip_p if res else None, rel_ind, ptr, edges, K)
+                r = F_.GcnEdgesFn.apply(y2, y3, skip_p if res else None, rel_ind, ptr, edges, K, *(self._bn_args(l, 2, 3) if fuse else no_bn), nxt_p)
+                new_p, p16n = (r[0], r[1].view(B * K, L)) if nxt_p else (r, None)
             x, p = new_x, new_p
             if tap is not None:                                     # dead outputs (None) are simply absent
                 if x is not None:

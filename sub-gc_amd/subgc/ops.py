@@ -707,20 +707,6 @@ def gcn_edges_bwd_bn(dP, F2, F3, aff2, aff3, ptr, edges, B, N, K, L, bf16=False)
     return dF2, dF3
 
 
-_IDENT_AFF = {}
-
-
-def identity_aff(L, device):
-    """The (mean | scale | shift) triple of the normalise-on-load aggregation kernels that changes nothing: (0 | 1 | 0)."""
-    key = (L, device)
-    t = _IDENT_AFF.get(key)
-    if t is None:
-        t = torch.zeros(3, L, device=device, dtype=torch.float32)
-        t[1].fill_(1.0)
-        _IDENT_AFF[key] = t
-    return t
-
-
 def _pool_account(denom, G, L, fwd):
     if FLOPS["on"]:                      # untimed accounting step: the valid node rows of every sub-graph (SURVEY 8d), not the padded N
         rows = float(denom[:G].cpu().sum())                  # host-side sum: the accounting step launches nothing of its own

@@ -99,7 +99,7 @@ def test_fused_bn_aggregation_fwd_bwd_matches_dense_reference(B, N, K, L, bf16):
     skip = torch.randn(B, N, L, device=DEV, requires_grad=True)
     (g0, b0), (g1, b1) = params(), params()
     stats = tuple(torch.zeros(L, device=DEV) if i % 2 == 0 else torch.ones(L, device=DEV) for i in range(4))
-    out, out16 = F_.GcnNodesBnFn.apply(y0, y1, skip, rel.to(DEV), ptr, edges, N, g0, b0, g1, b1, stats, True, True)
+    out, out16 = F_.GcnNodesFn.apply(y0, y1, skip, rel.to(DEV), ptr, edges, N, g0, b0, g1, b1, stats, True, True)
     want = (_collect(ref_bn(y0, g0, b0), maps[..., 0]) + _collect(ref_bn(y1, g1, b1), maps[..., 1])) / 2 + skip.double()
     np.testing.assert_allclose(out.detach().cpu().numpy(), want.detach().cpu().numpy(), **tol)
     np.testing.assert_allclose(out16.float().cpu().numpy(), out.detach().cpu().numpy(), atol=1e-2 * float(out.abs().max()), rtol=1e-2)
@@ -122,7 +122,7 @@ def test_fused_bn_aggregation_fwd_bwd_matches_dense_reference(B, N, K, L, bf16):
     skp = torch.randn(B, K, L, device=DEV, requires_grad=True)
     (g2, b2), (g3, b3) = params(), params()
     stats = tuple(torch.zeros(L, device=DEV) if i % 2 == 0 else torch.ones(L, device=DEV) for i in range(4))
-    outp = F_.GcnEdgesBnFn.apply(y2, y3, skp, rel.to(DEV), ptr, edges, K, g2, b2, g3, b3, stats, True, False)
+    outp = F_.GcnEdgesFn.apply(y2, y3, skp, rel.to(DEV), ptr, edges, K, g2, b2, g3, b3, stats, True, False)
     wantp = (_collect(ref_bn(y2, g2, b2), maps[..., 0].transpose(1, 2)) + _collect(ref_bn(y3, g3, b3), maps[..., 1].transpose(1, 2))) / 2 + skp.double()
     np.testing.assert_allclose(outp.detach().cpu().numpy(), wantp.detach().cpu().numpy(), **tol)
     w = torch.randn_like(outp)
@@ -138,8 +138,8 @@ def test_fused_bn_aggregation_fwd_bwd_matches_dense_reference(B, N, K, L, bf16):
 
 @pytest.mark.parametrize("B,N,K,L", [(3, 37, 65, 64), (2, 101, 301, 128)])
 def test_bf16_stored_unit_outputs_aggregate_like_their_fp32_values(B, N, K, L):
-    """compute_dtype = bf16 without BatchNorm (Sub-GC presets, Flickr shape): GcnNodesB16Fn / GcnEdgesB16Fn read the bf16 unit outputs
-    directly and write bf16 gradients -- same results as GcnNodesFn / GcnEdgesFn on the fp32 values of the same bf16 numbers, gradients
+    """compute_dtype = bf16 without BatchNorm (Sub-GC presets, Flickr shape): GcnNodesFn / GcnEdgesFn read the bf16 unit outputs
+    directly and write bf16 gradients -- same results as on the fp32 values of the same bf16 numbers, gradients
     equal after rounding to bf16, the bf16 copy of the result equal to the rounded result."""
     torch.manual_seed(B * N + 1)
     rel = _graph(B, N, K, B).to(DEV)
@@ -154,7 +154,7 @@ def test_bf16_stored_unit_outputs_aggregate_like_their_fp32_values(B, N, K, L):
     (y0, y0f), (y1, y1f) = pair((B, K, L)), pair((B, K, L))
     skip = torch.randn(B, N, L, device=DEV, requires_grad=True)
     skipf = skip.detach().clone().requires_grad_(True)
-    out, out16 = F_.GcnNodesB16Fn.apply(y0, y1, skip, rel, ptr, edges, N, True)
+    out, out16 = F_.GcnNodesFn.apply(y0, y1, skip, rel, ptr, edges, N, None, None, None, None, None, None, True)
     ref = F_.GcnNodesFn.apply(y0f, y1f, skipf, rel, ptr, edges, N)
     assert torch.equal(out, ref) and torch.equal(out16, ref.to(BFT))
     w = torch.randn_like(out)
@@ -165,7 +165,7 @@ def test_bf16_stored_unit_outputs_aggregate_like_their_fp32_values(B, N, K, L):
     (y2, y2f), (y3, y3f) = pair((B, N, L)), pair((B, N, L))
     skp = torch.randn(B, K, L, device=DEV, requires_grad=True)
     skpf = skp.detach().clone().requires_grad_(True)
-    outp = F_.GcnEdgesB16Fn.apply(y2, y3, skp, rel, ptr, edges, K, False)
+    outp = F_.GcnEdgesFn.apply(y2, y3, skp, rel, ptr, edges, K, None, None, None, None, None, None, False)
     refp = F_.GcnEdgesFn.apply(y2f, y3f, skpf, rel, ptr, edges, K)
     assert torch.equal(outp, refp)
     w = torch.randn_like(outp)
